@@ -11,10 +11,13 @@ frames are collected with ONE all_gather (RCCL) inside the timed region.  Launch
 ranks read RANK / LOCAL_RANK / WORLD_SIZE / MASTER_*; a plain `python bench.py --gpus N` launches them itself
 (self_launch_command).  Prints one JSON line on rank 0 (contract in the task statement).
 
+A plain run sets up, warms up, times the K steps and prints the line; everything else is measured only with --full:
 roofline: the dominant kernel family is the MFMA GEMM / implicit-conv / row-kernel family: its
 algorithmic FLOPs (2*M*N*K per launch, unpadded) over its summed launch durations, measured with
 HIP events on the launch stream during one instrumented UNet forward of the same workload.
 cpu_baseline: the fp32 CPU oracle timed on the host cores on a bounded sample of the same workload.
+Also only with --full: the single-clip stage breakdown, the text-encoder time and the stacked-vs-single-clip value check.
+--dump-outputs DIR: after the timed steps, the edited frames of the last timed step (what a caller receives) as DIR/frames.npy, fp32.
 """
 import argparse
 import json
@@ -151,7 +154,12 @@ def parse():
     ap.add_argument("--height", type=int, default=256)
     ap.add_argument("--width", type=int, default=384)
     ap.add_argument("--ddim-steps", type=int, default=50)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: stage breakdown, text-encoder time, stacked-vs-single check, "
+                         "roofline (an instrumented UNet forward) and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the edited frames of the last timed step to DIR/frames.npy (fp32; a fixed seeded sample if over 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--driver-mode", action="store_true",
                     help="time the units through the product driver's code (insv2v.run_loveu_tgve.edit_videos) instead of the bench's own stacking")
     ap.add_argument("--no-graph", action="store_true")
@@ -176,6 +184,15 @@ def parse():
                     help="config C4's unit: a 32-frame clip edited as 3 overlapping 16-frame windows (16 + 12 + 4 new frames, 4 / 12 "
                          "reference frames, mean-delta noise correction) through run_loveu_tgve.edit_video; not the headline metric")
     return ap.parse_args()
+
+
+def synth_weights(shapes_dict, threads=8):
+    """synth.synth_state_dict of a {key: shape} dict, the tensors drawn on host threads: every tensor has its own generator seeded
+    from its key, so the values are those of the serial form (1.3 G UNet values: ~10 s serial, under 2 s on 8 threads)."""
+    from concurrent.futures import ThreadPoolExecutor
+    from insv2v import synth
+    with ThreadPoolExecutor(max(1, min(threads, os.cpu_count() or 1))) as ex:
+        return dict(zip(shapes_dict, ex.map(lambda kv: synth.synth_tensor(*kv), shapes_dict.items())))
 
 
 def self_launch_command(gpus, argv, port=None):
@@ -214,11 +231,11 @@ def main():
     ucfg, vcfg = (synth.UNET_TINY, synth.VAE_TINY) if a.tiny else (synth.UNET_FULL, synth.VAE_FULL)
     ctx_dim = ucfg["cross_attention_dim"]
     model = create_model({"unet": {"params": ucfg}, "vae": {"params": vcfg}}, device=str(dev))
-    usd = synth.synth_state_dict(shapes.unet_shapes(**ucfg))
+    usd = synth_weights(shapes.unet_shapes(**ucfg))
     model.unet.load_state_dict(usd)
-    if not (rank == 0 and world == 1 and not a.no_cpu_baseline):
+    if not (rank == 0 and world == 1 and a.full and not a.no_cpu_baseline):
         del usd
-    model.vae.load_state_dict(synth.synth_state_dict(shapes.vae_shapes(**vcfg)))
+    model.vae.load_state_dict(synth_weights(shapes.vae_shapes(**vcfg)))
     if a.flow_correction:
         from insv2v.inference import InferenceIP2PVideoOpticalFlow as PipeCls
     else:
@@ -292,9 +309,10 @@ def main():
         torch.cuda.synchronize()
 
     for i in range(a.warmup):
-        one_unit(i, timed=(i == a.warmup - 1 and i > 0))  # stage breakdown from the last (already warm) warm-up unit
-    def units(idx):
-        """Edit len(idx) clips; their sampling loops are interleaved (independent units, clip-parallel on one GPU)."""
+        one_unit(i, timed=(a.full and i == a.warmup - 1 and i > 0))  # --full: stage breakdown from the last (already warm) warm-up unit
+    def units(idx, start_time=0):
+        """Edit len(idx) clips; their sampling loops are interleaved (independent units, clip-parallel on one GPU).
+        start_time > 0 skips the first DDIM steps (graph capture of a group shape; not for --driver-mode)."""
         if a.driver_mode:   # the product's own unit loop (run_loveu_tgve.edit_videos: VAE encode, stacked windows, VAE decode)
             from insv2v.run_loveu_tgve import edit_videos
             return edit_videos(model, pipe, [dict(frames=frames[i % len(frames)], text_cond=text_cond, text_uncond=text_uncond, text_cfg=7.5,
@@ -305,13 +323,16 @@ def main():
         run = pipe.run_stacked if a.clip_mode == "stacked" else pipe.run_concurrent
         extra = [dict(latent_ref=lref, noise_correct_step=0.5, **(dict(ref_images=ref_imgs, query_images=frames[i % len(frames)][:, R:]) if a.raft else dict(flows=flows)))
                  if a.flow_correction else {} for i in idx]
-        res = run([dict(latent=init, text_cond=text_cond, text_uncond=text_uncond, img_cond=c, text_cfg=7.5, img_cfg=1.5, **e) for c, e in zip(conds, extra)])
+        res = run([dict(latent=init, text_cond=text_cond, text_uncond=text_uncond, img_cond=c, text_cfg=7.5, img_cfg=1.5, start_time=start_time, **e)
+                   for c, e in zip(conds, extra)])
         return [model.decode_latent_to_image(r["latent"]).clip(-1, 1) for r in res]
 
     cc = a.concurrent_clips
-    for n in sorted(set(sizes), reverse=True):  # capture the graph of every group size outside the timed region
+    # capture the graph of every group size outside the timed region: the graph is one UNet forward of that shape, so the last
+    # DDIM step alone captures it (the driver's own loop has no start step: it runs whole units)
+    for n in sorted(set(sizes), reverse=True):
         if n > 1:
-            units(list(range(n)))
+            units(list(range(n)), start_time=0 if a.driver_mode else max(0, a.ddim_steps - 1))
     sync()
     t0 = time.perf_counter()
     outs, done = [], 0
@@ -329,10 +350,12 @@ def main():
         dist.all_reduce(el, op=dist.ReduceOp.MAX)
     elapsed = el.item()
     assert torch.isfinite(local_out.float()).all(), "non-finite output frames"
-    # outside the timed region: the first timed clip of a stacked group against the same clip edited alone (one launch chain per clip,
-    # other kernels at that launch shape) - the value-level check of what the timed region computed
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(a.dump_outputs, {"frames": outs[-1]})
+    # --full, outside the timed region: the first timed clip of a stacked group against the same clip edited alone (one launch chain per
+    # clip, other kernels at that launch shape) - the value-level check of what the timed region computed
     stacked_vs_single = None
-    if rank == 0 and plain and not a.long_video and sizes and sizes[0] > 1 and a.clip_mode == "stacked":
+    if a.full and rank == 0 and plain and not a.long_video and sizes and sizes[0] > 1 and a.clip_mode == "stacked":
         # the FIRST and the LAST clip of the first (largest) stack: the last one's rows lie beyond 2 GiB in the 960-wide operands of a
         # 20-clip stack, exactly where a 32-bit offset slip would show
         stacked_vs_single = 0.0
@@ -359,21 +382,39 @@ def main():
                        "frames": F, "height": H, "width": W, "ddim_steps": a.ddim_steps, "clips_per_gpu": a.steps,
                        "parallelism": f"clip-parallel x{world}, one all_gather", "hip_graph": not a.no_graph, "cfg_branch_streams": not a.no_branch_streams, "concurrent_clips": a.concurrent_clips, "clip_mode": a.clip_mode if a.concurrent_clips > 1 else "single", "clip_groups": sizes,
                        "stage_breakdown_note": "one clip alone (last warm-up unit: latency mode with the CFG branches batched), not the stacked groups",
-                       "stacked_vs_single_rel_rms": stacked_vs_single, "driver_mode": bool(a.driver_mode),
+                       "stacked_vs_single_rel_rms": stacked_vs_single, "driver_mode": bool(a.driver_mode), "full": bool(a.full),
                        "single_clip_latency": ({"ms_per_clip": round(sum(breakdown.values()), 1), "frames_per_s": round(F / max(sum(breakdown.values()), 1e-9) * 1e3, 3)}
                                                if breakdown else None),
                        "stage_breakdown_ms": {k: round(v, 2) for k, v in breakdown.items()}},
         }
-        if not a.tiny:
-            result["config"]["stage_breakdown_ms"]["text_encode_2_prompts_ms (outside the metric)"] = round(text_encode_ms(dev), 2)
-        nb = 3 * a.concurrent_clips if (a.concurrent_clips > 1 and a.clip_mode == "stacked") else 3
-        result["roofline"] = roofline(model, pipe, 16 if a.long_video else F, h, w, text_cond, text_uncond, dev, a, nb)   # long video: the 16-frame windows it launches
-        result["cpu_baseline"] = None
-        if world == 1 and not a.no_cpu_baseline:
-            result["cpu_baseline"] = cpu_baseline(ucfg, vcfg, usd, F, H, W, a.ddim_steps)
+        result["roofline"] = result["cpu_baseline"] = None
+        if a.full:
+            if not a.tiny:
+                result["config"]["stage_breakdown_ms"]["text_encode_2_prompts_ms (outside the metric)"] = round(text_encode_ms(dev), 2)
+            nb = 3 * a.concurrent_clips if (a.concurrent_clips > 1 and a.clip_mode == "stacked") else 3
+            result["roofline"] = roofline(model, pipe, 16 if a.long_video else F, h, w, text_cond, text_uncond, dev, a, nb)   # long video: the 16-frame windows it launches
+            if world == 1 and not a.no_cpu_baseline:
+                result["cpu_baseline"] = cpu_baseline(ucfg, vcfg, usd, F, H, W, a.ddim_steps)
         print(json.dumps(result), flush=True)
     if use_dist:
         dist.destroy_process_group()
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays, limit=DUMP_LIMIT_BYTES):
+    """Write each array as path/<name>.npy in fp32.  Together they stay within `limit` bytes: a larger output is replaced by a fixed
+    seeded sample of its flattened elements (the same positions in every run of the same arguments), written in flat index order."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    total = sum(t.numel() for t in arrays.values())
+    for name, t in arrays.items():
+        x = t.detach().float().cpu()
+        if total * 4 > limit:
+            keep = max(1, x.numel() * (limit // 4) // total)
+            x = x.reshape(-1)[torch.randperm(x.numel(), generator=torch.Generator().manual_seed(0))[:keep].sort().values]
+        np.save(os.path.join(path, name + ".npy"), x.numpy())
 
 
 def text_encode_ms(dev):

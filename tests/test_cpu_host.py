@@ -404,6 +404,38 @@ def test_bench_self_launch_command_and_no_gpu_exit():
         assert r.returncode != 0 and "GPU(s) visible" in r.stderr and "AssertionError" not in r.stderr, r.stderr[-500:]
 
 
+def test_bench_dump_outputs(tmp_path):
+    """bench.py --dump-outputs: every array as <name>.npy in fp32; within the byte limit the whole array, beyond it the same seeded
+    sample in every run (so two builds compare output for output)."""
+    import importlib.util
+    import numpy as np
+    spec = importlib.util.spec_from_file_location("bench_mod4", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    x = torch.randn(1, 4, 3, 8, 12, generator=torch.Generator().manual_seed(1)).half()
+    bench.dump_outputs(str(tmp_path / "a"), {"frames": x})
+    got = np.load(tmp_path / "a" / "frames.npy")
+    assert got.dtype == np.float32 and got.shape == tuple(x.shape) and np.array_equal(got, x.float().numpy())
+    assert bench.DUMP_LIMIT_BYTES == 64 << 20
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), {"frames": x}, limit=400)
+    b, c = np.load(tmp_path / "b" / "frames.npy"), np.load(tmp_path / "c" / "frames.npy")
+    assert b.dtype == np.float32 and b.nbytes <= 400 and b.size == 100 and np.array_equal(b, c)
+    assert np.isin(b, x.float().numpy().reshape(-1)).all()
+
+
+def test_bench_synth_weights_match_serial():
+    """bench.synth_weights draws the key-seeded tensors on host threads: same keys, order and values as synth.synth_state_dict."""
+    import importlib.util
+    from insv2v import synth, shapes
+    spec = importlib.util.spec_from_file_location("bench_mod5", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    shp = shapes.vae_shapes(**synth.VAE_TINY)
+    ref, got = synth.synth_state_dict(shp), bench.synth_weights(shp, threads=4)
+    assert list(got) == list(ref) and all(torch.equal(got[k], ref[k]) for k in ref)
+
+
 def test_xattn_fragment_streams_compute_the_cross_attention_block():
     """fused.pack_xattn_stream / pack_xattn_kv against a lane-level emulation of the schedule insv2v_xattn_fused runs (csrc/fused_rows.hip xa_op):
     v_mfma_f32_32x32x16_f16 operand / accumulator layouts, the C-layout -> operand chaining, head masking inside the K / V fragments."""

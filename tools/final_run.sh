@@ -15,7 +15,7 @@ cp $O/pmc_forward_traffic.json $R/profiles/pmc_forward_traffic.json
 # the driver's command line, with the board's power / shader clock sampled beside it (the kernels run power-limited)
 ( while true; do echo "smi $(date +%s.%N | cut -c1-14) $(rocm-smi --showpower --showclocks 2>/dev/null | grep -E 'sclk|Power' | tr -s ' \t' ' ' | tr '\n' ';')"; sleep 0.5; done ) > $O/smi_bench_steps20.log 2>&1 &
 SMI=$!
-( cd $R && timeout 1500 python bench.py --steps 20 --warmup 5 > $O/bench_steps20.json 2> $O/bench_steps20.err; tail -c 700 $O/bench_steps20.json )   # the driver's command line
+( cd $R && timeout 1500 python bench.py --full --steps 20 --warmup 5 > $O/bench_steps20.json 2> $O/bench_steps20.err; tail -c 700 $O/bench_steps20.json )   # the driver's command line
 kill $SMI
 python - $O/smi_bench_steps20.log > $O/smi_bench_steps20_summary.txt <<'PY'
 import re, sys
@@ -27,18 +27,18 @@ busy = [(p, c) for p, c in zip(pw, ck) if p > 0.6 * max(pw)] if pw else []
 print(f"{len(pw)} samples; while busy ({len(busy)} samples): power mean {sum(p for p, _ in busy) / max(len(busy), 1):.0f} W (max {max(pw) if pw else 0:.0f} W), sclk mean {sum(c for _, c in busy) / max(len(busy), 1):.0f} MHz (min {min((c for _, c in busy), default=0)}, max {max((c for _, c in busy), default=0)})")
 PY
 cat $O/smi_bench_steps20_summary.txt
-( cd $R && timeout 900 python bench.py --no-cpu-baseline > $O/bench.json 2> $O/bench.err; tail -c 300 $O/bench.json )
-( cd $R && timeout 1200 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --driver-mode > $O/bench_driver_mode.json 2> $O/bench_driver.err; tail -c 300 $O/bench_driver_mode.json )
-( cd $R && timeout 600 python bench.py --no-cpu-baseline --concurrent-clips 1 --steps 2 > $O/bench_single_clip.json 2> $O/bench_single.err; tail -c 300 $O/bench_single_clip.json )
+( cd $R && timeout 900 python bench.py --full --no-cpu-baseline > $O/bench.json 2> $O/bench.err; tail -c 300 $O/bench.json )
+( cd $R && timeout 1200 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --driver-mode > $O/bench_driver_mode.json 2> $O/bench_driver.err; tail -c 300 $O/bench_driver_mode.json )
+( cd $R && timeout 600 python bench.py --full --no-cpu-baseline --concurrent-clips 1 --steps 2 > $O/bench_single_clip.json 2> $O/bench_single.err; tail -c 300 $O/bench_single_clip.json )
 # the stacks the product meets below the bench's: C4's two units per GPU (B = 6), one video's four prompts (B = 12)
-( cd $R && timeout 600 python bench.py --no-cpu-baseline --concurrent-clips 2 --steps 4 --warmup 2 > $O/bench_b6.json 2> $O/bench_b6.err; tail -c 300 $O/bench_b6.json )
-( cd $R && timeout 600 python bench.py --no-cpu-baseline --concurrent-clips 4 --steps 8 --warmup 2 > $O/bench_b12.json 2> $O/bench_b12.err; tail -c 300 $O/bench_b12.json )
-( cd $R && timeout 900 python bench.py --flow-correction --steps 20 --warmup 2 --no-cpu-baseline > $O/bench_c3.json 2> $O/bench_c3.err; tail -c 300 $O/bench_c3.json )
-( cd $R && timeout 600 python bench.py --long-video --steps 1 --warmup 1 --no-cpu-baseline > $O/bench_long_video.json 2> $O/bench_long.err; tail -c 300 $O/bench_long_video.json )
-( cd $R && timeout 900 python bench.py --long-video --driver-mode --steps 4 --warmup 1 --no-cpu-baseline > $O/bench_long_video_driver.json 2> $O/bench_long_driver.err; tail -c 300 $O/bench_long_video_driver.json )
-( cd $R && timeout 900 python bench.py --frames 24 --height 384 --width 512 --steps 6 --warmup 2 --no-cpu-baseline > $O/bench_c5.json 2> $O/bench_c5.err; tail -c 300 $O/bench_c5.json )
+( cd $R && timeout 600 python bench.py --full --no-cpu-baseline --concurrent-clips 2 --steps 4 --warmup 2 > $O/bench_b6.json 2> $O/bench_b6.err; tail -c 300 $O/bench_b6.json )
+( cd $R && timeout 600 python bench.py --full --no-cpu-baseline --concurrent-clips 4 --steps 8 --warmup 2 > $O/bench_b12.json 2> $O/bench_b12.err; tail -c 300 $O/bench_b12.json )
+( cd $R && timeout 900 python bench.py --full --flow-correction --steps 20 --warmup 2 --no-cpu-baseline > $O/bench_c3.json 2> $O/bench_c3.err; tail -c 300 $O/bench_c3.json )
+( cd $R && timeout 600 python bench.py --full --long-video --steps 1 --warmup 1 --no-cpu-baseline > $O/bench_long_video.json 2> $O/bench_long.err; tail -c 300 $O/bench_long_video.json )
+( cd $R && timeout 900 python bench.py --full --long-video --driver-mode --steps 4 --warmup 1 --no-cpu-baseline > $O/bench_long_video_driver.json 2> $O/bench_long_driver.err; tail -c 300 $O/bench_long_video_driver.json )
+( cd $R && timeout 900 python bench.py --full --frames 24 --height 384 --width 512 --steps 6 --warmup 2 --no-cpu-baseline > $O/bench_c5.json 2> $O/bench_c5.err; tail -c 300 $O/bench_c5.json )
 for nb in 60 30 12 6 3; do ( cd $R && NB=$nb timeout 600 python tools/profile_unet.py > $O/unet_forward_per_shape_B$nb.txt 2>&1; head -2 $O/unet_forward_per_shape_B$nb.txt | tail -1 ); done
-timeout 900 rocprofv3 --kernel-trace --stats -d $O/stats -o ${TAG}f -- python $R/bench.py --steps 5 --warmup 1 --no-cpu-baseline > $O/bench_under_rocprof.json 2> $O/stats.err
+timeout 900 rocprofv3 --kernel-trace --stats -d $O/stats -o ${TAG}f -- python $R/bench.py --full --steps 5 --warmup 1 --no-cpu-baseline > $O/bench_under_rocprof.json 2> $O/stats.err
 G=$R/instruct-video-to-video_amd/build/gemm_check
 { echo "== big (8192^3, 4096^3): 230 gemm_q8, 232 without epilogue"; $G --set big --tiles 230,232 --iters 10
   echo "== unet60 (B = 60): 0 dispatch, 240 gemm_r8, 242 gemm_r8 without epilogue"; $G --set unet60 --tiles 0,240,242 --iters 5
