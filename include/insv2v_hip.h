@@ -263,9 +263,10 @@ int64_t insv2v_rowlin_stream_elems(int32_t N, int32_t K);
 /*
  * insv2v_tattn_fused: one temporal self-attention sub-block of TemporalTransformerBlock (motion_module.py:206,270-336:
  * LayerNorm -> (+ positional encoding) -> to_q / to_k / to_v -> scaled-dot-product attention over the frames of every pixel ->
- * to_out -> + residual) as ONE register-resident launch.  Supported: C = 320, 8 heads, exactly 16 frames (UNet level 0, every
- * 16-frame window); anything else returns INSV2V_EUNSUPPORTED and the caller uses insv2v_rowlin / insv2v_gemm + insv2v_attention.
- * x / out: token matrices [samples * 16 * HW, C] fp16 with rows ordered (sample, frame, pixel).  wstream: insv2v_tattn_stream_elems()
+ * to_out -> + residual) as ONE register-resident launch.  Supported: C = 320, 8 heads, windows of 1 ... 32 frames (UNet level 0; the
+ * stream layout holds 16 frame slots for 1 ... 16 frames and 32 for 17 ... 32, rows of padded slots are neither read nor written);
+ * anything else returns INSV2V_EUNSUPPORTED and the caller uses insv2v_rowlin / insv2v_gemm + insv2v_attention.
+ * x / out: token matrices [samples * frames * HW, C] fp16 with rows ordered (sample, frame, pixel).  wstream: insv2v_tattn_stream_elems()
  * fp16 elements from insv2v/fused.py pack_tattn_stream (q/k/v weights with the LayerNorm gamma folded in, the per-frame bias table
  * = positional-encoding rows pushed through the weights + W beta, the output projection and its bias).
  */
@@ -280,7 +281,7 @@ typedef struct insv2v_tattn_desc {
 } insv2v_tattn_desc;
 int insv2v_tattn_fused(const insv2v_tattn_desc* d, insv2v_stream_t stream);
 int64_t insv2v_tattn_stream_elems(int32_t C, int32_t heads, int32_t frames);
-/* The same sub-block at C = 640 (8 heads x 80, 16 frames) WITHOUT the output projection (ABI 8): out [rows, C] = the attention output
+/* The same sub-block at C = 640 (8 heads x 80, 1 ... 32 frames) WITHOUT the output projection (ABI 8): out [rows, C] = the attention output
  * (LayerNorm -> q/k/v with the per-frame bias -> softmax over the frames -> P.V); to_out + residual follow as insv2v_rowlin.  q, k and v
  * never exist in memory.  Same descriptor; wstream: insv2v_tattn_attn_stream_elems(C, heads, frames) halfs (insv2v/fused.py
  * pack_tattn_qkv_stream). */

@@ -102,14 +102,26 @@ def pack_ffn_stream(w1f, b1f, w2, b2, post=None):
     return torch.cat(parts, 0).reshape(-1).half()
 
 
-def _frame_frag(table_rows):
-    """Per-frame bias table restricted to one 32-row block, [F <= 16, 32] fp32 -> [64, 8] fragment for the one-hot-of-frame k-step:
-    lane (row i, half), slot jj = table[8 half + jj][i] (fp16)."""
+def _frame_frag(table_rows, step=0):
+    """Per-frame bias table restricted to one 32-row block, [F <= 32, 32] fp32 -> [64, 8] fragment for one-hot-of-frame k-step ``step``
+    (frames 16 step .. 16 step + 15): lane (row i, half), slot jj = table[16 step + 8 half + jj][i] (fp16), zero beyond F."""
     F = table_rows.shape[0]
     f = torch.zeros(2, 32, 8)
-    for fr in range(F):
-        f[fr >> 3, :, fr & 7] = table_rows[fr].half().float()
+    for fr in range(16 * step, min(F, 16 * step + 16)):
+        f[(fr >> 3) & 1, :, fr & 7] = table_rows[fr].half().float()
     return f.reshape(64, 8)
+
+
+def _tattn_frame_slots(table):
+    """Frame slots of the fused temporal-attention kernels for a window of table.shape[0] frames: 16 (1 .. 16 frames) or 32 (17 .. 32)."""
+    F = table.shape[0]
+    assert 1 <= F <= 32, F
+    return 16 if F <= 16 else 32
+
+
+def _tattn_tile(w_rows, table_rows, kn, nb):
+    """[KS + nb, 64, 8]: the fragments of one q / k / v channel tile - the weight k-steps, then nb one-hot frame-bias steps."""
+    return torch.cat([_frags(w_rows, kn)] + [_frame_frag(table_rows, j)[None] for j in range(nb)], 0)
 
 
 def pack_linear_stream(w, bias=None, table=None):
@@ -140,26 +152,30 @@ def pack_linear_stream(w, bias=None, table=None):
 
 
 def pack_tattn_stream(wqkv, table, wo, bo):
-    """Weight stream of insv2v_tattn_fused (C = 320, 8 heads x 40, 16 frames).
-    wqkv [3C, C]: fused to_q / to_k / to_v weights with the LayerNorm gamma folded in (fp16-valued); table [16, 3C] fp32: per-frame bias
+    """Weight stream of insv2v_tattn_fused (C = 320, 8 heads x 40, a window of F = 1 .. 32 frames).
+    wqkv [3C, C]: fused to_q / to_k / to_v weights with the LayerNorm gamma folded in (fp16-valued); table [F, 3C] fp32: per-frame bias
     (positional-encoding rows pushed through the weights + W beta); wo [C, C], bo [C]: output projection.
+    F <= 16: 16 frame slots, NB = 1 frame-bias step per q/k/v tile; 17 <= F <= 32: 32 frame slots, NB = 2; table rows beyond F are zero.
     Layout (fragments; the kernel's ta_op schedule): for head group G = 0, 1 (channel tiles c = 5G .. 5G+4):
-    [for tile c: for k-step s = 0..20: (q, k)] [v tiles (5G, 5G+1) interleaved over s] [v tiles (5G+2, 5G+3)] [v tile 5G+4] [pad 5];
-    then [output tiles in pairs, interleaved over s] [pad 14].  s = 20 is the bias step (frame table for q/k/v, hi + lo bias for the
-    output).  q/k/v read x from memory (natural k order); the output projection consumes the attention result in the C-layout order."""
+    [for tile c: for k-step s = 0..19+NB: (q, k)] [v tiles (5G, 5G+1) interleaved over s] [v tiles (5G+2, 5G+3)] [v tile 5G+4]
+    [pad to a multiple of 16: 5 / 6]; then [output tiles in pairs, interleaved over s = 0..20] [pad 14].  s >= 20 are the bias steps
+    (frame table for q/k/v, hi + lo bias for the output).  q/k/v read x from memory (natural k order); the output projection consumes the
+    attention result in the C-layout order."""
     wqkv, table, wo, bo = wqkv.detach().float().cpu(), table.detach().float().cpu(), wo.detach().float().cpu(), bo.detach().float().cpu()
     C = wo.shape[0]
-    assert wqkv.shape == (3 * C, C) and table.shape == (16, 3 * C) and C == 320
+    assert wqkv.shape == (3 * C, C) and table.shape[1] == 3 * C and C == 320
+    nb = _tattn_frame_slots(table) // 16
     KS = C // 16
     kn, kc = _kperm_nat(KS), _kperm(KS)
 
-    def tile(which, c):      # [KS + 1, 64, 8]: the 21 fragments of q (0) / k (1) / v (2) channel tile c
+    def tile(which, c):      # [KS + nb, 64, 8]: the fragments of q (0) / k (1) / v (2) channel tile c
         rows = slice(which * C + 32 * c, which * C + 32 * c + 32)
-        return torch.cat([_frags(wqkv[rows], kn), _frame_frag(table[:, rows])[None]], 0)
+        return _tattn_tile(wqkv[rows], table[:, rows], kn, nb)
 
     def inter(a, b):         # interleave two tiles' fragments over the k-steps
         return torch.stack([a, b], dim=1).reshape(-1, 64, 8)
 
+    sec = 15 * (KS + nb)
     parts = []
     for G in range(2):
         for tl in range(5):
@@ -167,33 +183,36 @@ def pack_tattn_stream(wqkv, table, wo, bo):
         parts.append(inter(tile(2, 5 * G), tile(2, 5 * G + 1)))
         parts.append(inter(tile(2, 5 * G + 2), tile(2, 5 * G + 3)))
         parts.append(tile(2, 5 * G + 4))
-        parts.append(torch.zeros(5, 64, 8))
+        parts.append(torch.zeros((sec + 15) // 16 * 16 - sec, 64, 8))
     for p in range(5):
         t = [torch.cat([_frags(wo[32 * (2 * p + j):32 * (2 * p + j) + 32], kc), _bias_frag(bo[32 * (2 * p + j):32 * (2 * p + j) + 32])[None]], 0) for j in range(2)]
         parts.append(inter(t[0], t[1]))
     parts.append(torch.zeros(14, 64, 8))
     out = torch.cat(parts, 0)
-    assert out.shape[0] == 864
+    assert out.shape[0] == (864 if nb == 1 else 896)
     return out.reshape(-1).half()
 
 
 def pack_tattn_qkv_stream(wqkv, table):
-    """Weight stream of insv2v_tattn_attn (C = 640, 8 heads x 80, 16 frames): wqkv [3C, C] fused to_q / to_k / to_v with the LayerNorm gamma
-    folded in (fp16-valued); table [16, 3C] fp32 per-frame bias.  Layout (fragments; the kernel's tb_op schedule), for head group G = 0..3
-    (2 heads = channel tiles c = 5G .. 5G+4): [for tile c: for k-step s = 0..40: (q, k)] [v tiles (5G, 5G+1) interleaved over s]
-    [v tiles (5G+2, 5G+3)] [v tile 5G+4] [pad 9]; s = 40 is the frame-table step; natural k order (x is read from memory)."""
+    """Weight stream of insv2v_tattn_attn (C = 640, 8 heads x 80, a window of F = 1 .. 32 frames): wqkv [3C, C] fused to_q / to_k / to_v with
+    the LayerNorm gamma folded in (fp16-valued); table [F, 3C] fp32 per-frame bias (F <= 16: NB = 1 frame-bias step per tile, 17 .. 32:
+    NB = 2).  Layout (fragments; the kernel's tb_op schedule), for head group G = 0..3 (2 heads = channel tiles c = 5G .. 5G+4):
+    [for tile c: for k-step s = 0..39+NB: (q, k)] [v tiles (5G, 5G+1) interleaved over s] [v tiles (5G+2, 5G+3)] [v tile 5G+4]
+    [pad 9 / 10]; s >= 40 are the frame-table steps; natural k order (x is read from memory)."""
     wqkv, table = wqkv.detach().float().cpu(), table.detach().float().cpu()
     C = wqkv.shape[1]
-    assert wqkv.shape == (3 * C, C) and table.shape == (16, 3 * C) and C == 640
+    assert wqkv.shape == (3 * C, C) and table.shape[1] == 3 * C and C == 640
+    nb = _tattn_frame_slots(table) // 16
     kn = _kperm_nat(C // 16)
 
-    def tile(which, c):
+    def tile(which, c):      # [40 + nb, 64, 8]
         rows = slice(which * C + 32 * c, which * C + 32 * c + 32)
-        return torch.cat([_frags(wqkv[rows], kn), _frame_frag(table[:, rows])[None]], 0)      # [41, 64, 8]
+        return _tattn_tile(wqkv[rows], table[:, rows], kn, nb)
 
     def inter(a, b):
         return torch.stack([a, b], dim=1).reshape(-1, 64, 8)
 
+    sec = 15 * (C // 16 + nb)
     parts = []
     for G in range(4):
         for tl in range(5):
@@ -201,9 +220,9 @@ def pack_tattn_qkv_stream(wqkv, table):
         parts.append(inter(tile(2, 5 * G), tile(2, 5 * G + 1)))
         parts.append(inter(tile(2, 5 * G + 2), tile(2, 5 * G + 3)))
         parts.append(tile(2, 5 * G + 4))
-        parts.append(torch.zeros(9, 64, 8))
+        parts.append(torch.zeros((sec + 15) // 16 * 16 - sec, 64, 8))
     out = torch.cat(parts, 0)
-    assert out.shape[0] == 4 * 624
+    assert out.shape[0] == 4 * (624 if nb == 1 else 640)
     return out.reshape(-1).half()
 
 

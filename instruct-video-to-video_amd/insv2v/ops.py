@@ -253,13 +253,13 @@ def rowlin(x, wstream, N, *, layernorm=False, residual=None, frames=0, rows_per_
 
 
 def tattn_fused_supported(C, heads, frames):
-    """True if insv2v_tattn_fused handles this temporal attention block (C = 320, 8 heads, exactly 16 frames)."""
+    """True if insv2v_tattn_fused handles this temporal attention block (C = 320, 8 heads, a window of 1 .. 32 frames)."""
     return int(_lib.load().insv2v_tattn_stream_elems(C, heads, frames)) > 0
 
 
 def tattn_fused(x, wstream, samples, HW, heads, frames, eps=1e-5, out=None):
     """out = x + to_out(attention over the frames(LayerNorm(x) + pe -> q, k, v)) in one launch (insv2v_tattn_fused); x rows ordered
-    (sample, frame, pixel); wstream from fused.pack_tattn_stream."""
+    (sample, frame, pixel); wstream from fused.pack_tattn_stream with a table of `frames` rows."""
     lib = _lib.load()
     _req(x, torch.float16, "tattn.x"), _req(wstream, torch.float16, "tattn.wstream")
     M, C = x.shape
@@ -278,13 +278,13 @@ def tattn_fused(x, wstream, samples, HW, heads, frames, eps=1e-5, out=None):
 
 
 def tattn_attn_supported(C, heads, frames):
-    """True if insv2v_tattn_attn handles this temporal attention block (C = 640, 8 heads, exactly 16 frames)."""
+    """True if insv2v_tattn_attn handles this temporal attention block (C = 640, 8 heads, a window of 1 .. 32 frames)."""
     return int(_lib.load().insv2v_tattn_attn_stream_elems(C, heads, frames)) > 0
 
 
 def tattn_attn(x, wstream, samples, HW, heads, frames, eps=1e-5, out=None):
     """out = attention over the frames(LayerNorm(x) + pe -> q, k, v), WITHOUT to_out / residual, in one launch (insv2v_tattn_attn, C = 640);
-    x rows ordered (sample, frame, pixel); wstream from fused.pack_tattn_qkv_stream."""
+    x rows ordered (sample, frame, pixel); wstream from fused.pack_tattn_qkv_stream with a table of `frames` rows."""
     lib = _lib.load()
     _req(x, torch.float16, "tattn_attn.x"), _req(wstream, torch.float16, "tattn_attn.wstream")
     M, C = x.shape

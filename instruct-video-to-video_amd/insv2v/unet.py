@@ -59,11 +59,15 @@ ROWLIN_640_MIN_ROWS = int(os.environ.get("INSV2V_ROWLIN_640_MIN_ROWS", "55296"))
 
 def _rowlin_640_pays(rows):
     return rows >= ROWLIN_640_MIN_ROWS or rows < 12288
-# Temporal attention sub-block (LayerNorm -> q/k/v -> attention over 16 frames -> to_out -> + residual) as one register-resident launch
+# Temporal attention sub-block (LayerNorm -> q/k/v -> attention over the frames -> to_out -> + residual) as one register-resident launch
 # at C = 320 (insv2v_tattn_fused); INSV2V_FUSE_TATTN=0 restores row-linear + attention + row-linear for A/B runs.
 FUSE_TATTN = os.environ.get("INSV2V_FUSE_TATTN", "1") != "0"
 # C = 640: LayerNorm -> q/k/v -> attention as one launch (insv2v_tattn_attn), to_out + residual as a row Linear; =0 for A/B runs
 FUSE_TATTN_640 = os.environ.get("INSV2V_FUSE_TATTN_640", "1") != "0"
+# Shortest window the two fused temporal kernels take (they handle 1 .. 32 frames).  Below 16 frames the masked 16-slot form spends the
+# padding slots' share of its projection MFMAs for nothing, and the row-linear + short-attention route is kept;
+# INSV2V_TATTN_MIN_FRAMES=1 sends short windows through the fused kernels for A/B runs.
+TATTN_MIN_FRAMES = int(os.environ.get("INSV2V_TATTN_MIN_FRAMES", "16"))
 # GroupNorm of the transformer blocks applied inside the proj_in row kernel (statistics pass only, no normalised copy)
 ROWLIN_GN = os.environ.get("INSV2V_ROWLIN_GN", "1") != "0"
 # text cross-attention sub-block (LayerNorm -> q -> attention over the text tokens -> out-proj + residual) as ONE launch at C = 320
@@ -469,12 +473,17 @@ class MotionModule:
             start -= self.max_len
         if start < 0:
             raise ValueError(f"start_index must be non-negative, but got {start}")
-        # The per-frame bias step of insv2v_rowlin (and the fused attention blocks) hold 16 frames.  Longer windows (BASELINE config C5: 24
-        # frames) keep the row kernels for everything that needs no frame table - GroupNorm + proj_in, the output projections with their
-        # residuals, the fused feed-forward, proj_out - and take the folded-LayerNorm GEMM with a per-frame row bias + the generic
-        # attention kernel for q/k/v only (round 4; round 3 sent the whole module down the generic path).
+        # The per-frame bias step of insv2v_rowlin holds 16 frames (rl_frames); the fused attention kernels take windows of 1 .. 32 frames.
+        # A window either of them covers runs the same launch sequence as 16 frames (no statistics pass, q / k / v never in memory).
+        # Elsewhere (C = 1280, or INSV2V_FUSE_TATTN*=0 with more than 16 frames) the row kernels keep everything that needs no frame
+        # table - GroupNorm + proj_in, the output projections with their residuals, the fused feed-forward, proj_out - and q/k/v take the
+        # folded-LayerNorm GEMM with a per-frame row bias + the generic attention kernel.
         rl = self.rl if (C != 640 or _rowlin_640_pays(x.t.shape[0])) else None
         rl_frames = rl is not None and F <= 16
+        win = rl is not None and F >= TATTN_MIN_FRAMES
+        fused_attn = win and FUSE_TATTN and ops.tattn_fused_supported(C, self.heads, F)
+        fused_640 = win and FUSE_TATTN_640 and ops.tattn_attn_supported(C, self.heads, F)
+        row_flow = rl_frames or fused_attn or fused_640   # no folded-LayerNorm q/k/v GEMM, so no LayerNorm statistics passes
         if rl is not None and ROWLIN_GN and HW % 32 == 0:
             ab = ops.groupnorm_stats(x.t, x.B * F, HW, *self.norm, self.groups, 1e-6)
             h, st = ops.rowlin(x.t, rl["proj_in"], C, gn_ab=ab, gn_rows=HW), None
@@ -482,16 +491,15 @@ class MotionModule:
             h, st = ops.rowlin(ops.groupnorm(x.t, x.B * F, HW, *self.norm, self.groups, 1e-6), rl["proj_in"], C), None
         else:
             h, st = ops.gemm(ops.groupnorm(x.t, x.B * F, HW, *self.norm, self.groups, 1e-6), *self.proj_in, emit_stats=True)
-        if rl is not None and not rl_frames:
+        if rl is not None and not row_flow:
             st = ops.layernorm_stats(h)   # the q/k/v GEMM folds the LayerNorm: statistics of the proj_in rows
-        fused_attn = rl_frames and FUSE_TATTN and ops.tattn_fused_supported(C, self.heads, F)
         for bi, blk in enumerate(self.blocks):
             for at in blk["attns"]:
                 if fused_attn:   # the whole sub-block in one launch: q / k / v never exist in memory
                     h = ops.tattn_fused(h, self._tattn_stream(at, start, F), x.B, HW, self.heads, F)
                     continue
                 pe_half = None
-                if rl_frames and FUSE_TATTN_640 and ops.tattn_attn_supported(C, self.heads, F) and h.is_contiguous():
+                if fused_640 and h.is_contiguous():
                     # C = 640: LayerNorm -> q/k/v -> attention in one launch (q, k, v never exist in memory), then to_out + residual
                     a = ops.tattn_attn(h, self._tattn_qkv_stream(at, start, F), x.B, HW, self.heads, F)
                     if blk["ff"].stream is None and at is blk["attns"][-1]:
@@ -499,6 +507,8 @@ class MotionModule:
                     else:
                         h = ops.rowlin(a, at["rl_wo"], C, residual=h)
                     continue
+                if not rl_frames and rl is not None and st is None:   # (a long window whose fused kernel was passed over after all)
+                    st = ops.layernorm_stats(h)                          # the q/k/v GEMM below folds the LayerNorm
                 if rl_frames:
                     qkv = ops.rowlin(h, self._qkv_stream(at, start, F), 3 * C, layernorm=True, frames=F, rows_per_frame=HW)
                 elif ATTN_PE_BIAS and ops.attention_short_supported(self.heads, hd, F):
@@ -529,7 +539,7 @@ class MotionModule:
             if bi + 1 == len(self.blocks) and blk["ff"].w2p is not None:
                 return x.like(blk["ff"].with_proj_out_gemm(h, st, x.t))
             h = blk["ff"](h, h, st)
-            if bi + 1 < len(self.blocks) and not rl_frames:  # a further transformer block starts from a statistics pass over the FF output
+            if bi + 1 < len(self.blocks) and not row_flow:  # a further transformer block starts from a statistics pass over the FF output
                 st = ops.layernorm_stats(h)
         if rl is not None:
             return x.like(ops.rowlin(h, rl["proj_out"], C, residual=x.t))
