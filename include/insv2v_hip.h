@@ -228,7 +228,7 @@ int64_t insv2v_ffn_stream_elems(int32_t C, int32_t hidden, int32_t post);
 
 /*
  * insv2v_rowlin: out = [LayerNorm](x) W^T + bias [+ residual] for the K = 320 / 640 Linear / 1x1-conv layers (UNet levels 0-1), activations
- * resident in registers (same machinery as insv2v_ffn_fused; csrc/fused_rows.hip): Transformer3DModel / TemporalTransformer3DModel
+ * resident in registers (same machinery as insv2v_ffn_fused; csrc/rows_common.h): Transformer3DModel / TemporalTransformer3DModel
  * proj_in / proj_out (attention.py:64,89; motion_module.py:139,146), Attention.to_q / to_k / to_v / to_out
  * (attention.py:160-190, motion_module.py:289-331).  K must be 320 or 640 and N a multiple of 64, else INSV2V_EUNSUPPORTED (use insv2v_gemm).
  *   layernorm != 0: x is normalised per row in registers (no affine: gamma is folded into W and beta into the bias by the caller,

@@ -437,7 +437,7 @@ def test_bench_synth_weights_match_serial():
 
 
 def test_xattn_fragment_streams_compute_the_cross_attention_block():
-    """fused.pack_xattn_stream / pack_xattn_kv against a lane-level emulation of the schedule insv2v_xattn_fused runs (csrc/fused_rows.hip xa_op):
+    """fused.pack_xattn_stream / pack_xattn_kv against a lane-level emulation of the schedule insv2v_xattn_fused runs (csrc/rows_xattn.hip xa_op):
     v_mfma_f32_32x32x16_f16 operand / accumulator layouts, the C-layout -> operand chaining, head masking inside the K / V fragments."""
     import torch
     from insv2v import fused
@@ -526,7 +526,7 @@ def test_xattn_fragment_streams_compute_the_cross_attention_block():
 
 
 def test_xattn640_fragment_streams_compute_the_cross_attention():
-    """fused.pack_xattn_q_stream / pack_xattn640_kv against a lane-level emulation of the schedule insv2v_xattn_attn runs (csrc/fused_rows.hip
+    """fused.pack_xattn_q_stream / pack_xattn640_kv against a lane-level emulation of the schedule insv2v_xattn_attn runs (csrc/rows_xattn.hip
     xb_op): per 160-channel head group the q tiles, then per head 15 K and 18 V fragments; heads of 80 channels = 5 whole k-steps."""
     import torch
     from insv2v import fused
@@ -600,7 +600,7 @@ def test_xattn640_fragment_streams_compute_the_cross_attention():
 
 
 def test_tattn640_fragment_stream_computes_the_temporal_attention():
-    """fused.pack_tattn_qkv_stream against a lane-level emulation of the schedule insv2v_tattn_attn runs (csrc/fused_rows.hip tb_op): a wave = 2
+    """fused.pack_tattn_qkv_stream against a lane-level emulation of the schedule insv2v_tattn_attn runs (csrc/rows_tattn.hip tb_op): a wave = 2
     pixels x 16 frames; per 160-channel group the q / k tiles (weights as the A operand), S^T = K . Q^T with the two pixels on the diagonal
     16x16 blocks, V with the operands swapped so its packed tile is the A operand of O^T = V^T . P^T; per-frame bias through the one-hot k-step."""
     import torch

@@ -1,4 +1,4 @@
-"""CPU tests of the fused temporal-attention streams for windows of 1 .. 32 frames (csrc/fused_rows.hip insv2v_tattn_fused / insv2v_tattn_attn):
+"""CPU tests of the fused temporal-attention streams for windows of 1 .. 32 frames (csrc/rows_tattn.hip insv2v_tattn_fused / insv2v_tattn_attn):
 the packers against the library's stream sizes, the 16-frame streams byte-for-byte as before, and a lane-level emulation of the 32-slot
 and the masked 16-slot wave schedules over the packed stream against fp32 attention."""
 import hashlib

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """The register-resident row kernels at the token counts of a stacked forward (default B = 60), one line per launch shape: for A/B builds
-of csrc/fused_rows.hip (INSV2V_LIB=path/to/other/libinsv2v_hip.so python tools/bench_rows_ab.py) on one box."""
+of csrc/rows_ffn.hip / rows_tattn.hip / rows_xattn.hip (INSV2V_LIB=path/to/other/libinsv2v_hip.so python tools/bench_rows_ab.py) on one box."""
 import os
 import sys
 

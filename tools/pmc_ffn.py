@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""A few launches of the fused feed-forward (and nothing else) for rocprofv3 --pmc passes; INSV2V_FFN_DBG selects the variant."""
+"""A few launches of the fused feed-forward (and nothing else) for rocprofv3 --pmc passes."""
 import os
 import sys
 

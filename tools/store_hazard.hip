@@ -1,5 +1,5 @@
 // store_hazard: minimal stand-alone probe of the gfx950 hazard behind the `s_nop 7` / pinned-register workarounds in the persistent GEMM
-// epilogues (gemm_p8 / gemm_q8 / gemm_r8 / gemm_w4 / fused_rows: profiles/r02_gemm_debug.md, VERDICT r3 "weak" item 14).
+// epilogues (gemm_p8 / gemm_q8 / gemm_r8 / gemm_w4 / rows_common.h: profiles/r02_gemm_debug.md, VERDICT r3 "weak" item 14).
 //
 //   build : hipcc --offload-arch=gfx950 -O3 -std=c++17 tools/store_hazard.hip -o instruct-video-to-video_amd/build/store_hazard
 //           (the kernels are hand-written inline asm, so what is measured is exactly the instruction sequence printed below)
