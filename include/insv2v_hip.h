@@ -65,6 +65,10 @@ int insv2v_init(void);
  *   M = NB*OH*OW, K = 9*Cin, W is [N, 3,3,Cin]. Input pixel for output (oh,ow), tap (kh,kw) is
  *   (oh*stride+kh-pad_t, ow*stride+kw-pad_l), zero outside; with upsample=1 the input is first
  *   nearest-x2 upsampled (index>>1) without materialising it. Channel concat via k_split (=C1).
+ *   (ABI 13) upsample=1 is valid only with stride = 1, pad_t = pad_l = 1 and OH in {2*IH-1, 2*IH}, OW in {2*IW-1, 2*IW}
+ *   (anything else: INSV2V_EINVAL).  OH x OW is the extent of the upsampled image: 2*IH-1 / 2*IW-1 is the x2 image WITHOUT its
+ *   last row / column (F.interpolate(size=..., mode="nearest") for those sizes, Upsample3D's output_size, resnet.py:41-61) and the
+ *   zero padding sits at that cropped edge - not "convolve the x2 image, then crop".  The patch-tiled kernel takes exact x2 only.
  *   Cin must be a multiple of 64 (pad channels on the host) and k_split a multiple of 64.
  *   Replaces F.conv2d at resnet.py:10-18 (InflatedConv3d), :59-69 (Upsample3D), :87-105
  *   (Downsample3D), unet.py:92,225 and vqvae/model.py:35-74,77-136 (VAE convs incl. the
@@ -163,13 +167,14 @@ int insv2v_conv3x3_fuses_groupnorm(const insv2v_gemm_desc* d);
  * InflatedConv3d resnet.py:10-18; ABI 11).  y = A^T [ sum_c (G g G^T) . (B^T d B) ] A per 2x2 output tile: 2.25 x fewer MACs.  Three calls:
  *   insv2v_winograd_input  : x [NB*H*W, C] (channel concat x | x2 at C1; optional GroupNorm scale / shift table gn_ab [nsamples][C][2] as
  *                            from insv2v_groupnorm(stats_only), then SiLU - resnet.py:177-178,188; zero padding applies AFTER the norm)
- *                            -> v = 16 matrices V_k [tiles, C], matrix k = i*4 + j at row offset k * v_group_rows (tiles = NB*(H/2)*(W/2),
+ *                            -> v = 16 matrices V_k [tiles, C], matrix k = i*4 + j at row offset k * v_group_rows (tiles = NB*ceil(H/2)*ceil(W/2),
  *                            tile order (image, ty, tx); v_group_rows >= tiles, a multiple of 256 for the grouped GEMM)
  *   insv2v_gemm            : a = v [16 * v_group_rows, C], w = U [16][Cout][C] (U_k = (G g G^T)_k, host), w_group_rows = v_group_rows,
  *                            w_group_stride = Cout * C  ->  m [16 * v_group_rows, Cout] fp16
  *   insv2v_winograd_output : m -> y [NB*H*W, Cout] fp16 = A^T M A + bias[Cout] + row_bias[(pixel / rows_per_group) * ld_rb + n]
  *                            (time embedding, resnet.py:183-186) + residual[pixel * ldr + n]
- * H, W even; C a multiple of 64 (C1 too); W <= 128 (an image's 64-channel slice is staged in LDS whole, or in bands of tile rows with a
+ * H, W of either parity ((ABI 13) odd: the last tile row / column hangs over the image, reads zeros there and stores only the pixels that exist;
+ * the upsample form is exact x2 only); C a multiple of 64 (C1 too); W <= 128 (an image's 64-channel slice is staged in LDS whole, or in bands of tile rows with a
  * one-pixel halo); else INSV2V_EUNSUPPORTED and the caller uses insv2v_gemm CONV3X3.  fp16 storage of V, U, M: 6.5e-4 of max|ref| vs fp32 conv2d (profiles/r06_winograd_proto.txt).
  */
 typedef struct insv2v_winograd_in_desc {
@@ -426,6 +431,11 @@ int insv2v_embed_tokens(const int64_t* ids, const void* tok, const void* pos, vo
  * vqvae/model.py:186-188): y = softmax(x * scale) along cols. */
 int insv2v_softmax_rows(const void* x, void* y, int64_t ldx, int64_t ldy, int32_t rows, int32_t cols,
                         float scale, insv2v_stream_t stream);
+/* (ABI 13) The same over the first `valid` of `cols` columns (cols a multiple of 8): columns [valid, cols) are not read as values and are
+ * written as exact zeros - the score matrix of a VAE AttnBlock whose h*w is not a multiple of 8, with its leading dimension padded to 8
+ * so that P.V may contract over all `cols` columns (v^T's pad columns are zero too). */
+int insv2v_softmax_rows_padded(const void* x, void* y, int64_t ldx, int64_t ldy, int32_t rows, int32_t cols, int32_t valid,
+                               float scale, insv2v_stream_t stream);
 
 /* Sinusoidal timestep features (diffusers Timesteps(dim, flip_sin_to_cos=True, shift) as used at
  * unet.py:95,358): out[b, :] = [cos(t*f_k), sin(t*f_k)] fp16, t read from device memory t[b] (fp32). */

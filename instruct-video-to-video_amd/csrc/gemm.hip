@@ -415,7 +415,7 @@ __global__ __launch_bounds__(WM * WN * KG * 64) void gemm_kernel(insv2v_gemm_des
     const int nk_per = (nk_total + nsplit - 1) / nsplit;
     const int kt0 = zs * nk_per;
     const int nk = max(0, min(nk_per, nk_total - kt0));
-    const int IHu = p.upsample ? p.IH * 2 : p.IH, IWu = p.upsample ? p.IW * 2 : p.IW;
+    const int IHu = p.upsample ? p.OH : p.IH, IWu = p.upsample ? p.OW : p.IW;   // upsample: the (possibly cropped) nearest-x2 image IS the output extent (stride 1, pad 1)
 
     // Slices are requested in increasing order: everything slice-dependent is a wave-uniform scalar
     // kept in a cursor (no division, no 64-bit arithmetic in the loop).
@@ -1184,6 +1184,10 @@ extern "C" int insv2v_gemm(const insv2v_gemm_desc* dp, insv2v_stream_t stream) {
     if (d.mode == INSV2V_MODE_CONV3X3) {
         if (d.Cin <= 0 || (d.Cin % BK) || d.K != 9 * d.Cin) return INSV2V_EINVAL;
         if ((long)d.NB * d.OH * d.OW != d.M || d.stride < 1) return INSV2V_EINVAL;
+        // nearest-x2 upsample to an explicit output size (Upsample3D's output_size, resnet.py:41-61): the x2 image or that image without its last
+        // row / column; the gather kernels zero-pad at the REQUESTED extent, and index >> 1 of any tap inside it is inside the input
+        if (d.upsample && (d.stride != 1 || d.pad_t != 1 || d.pad_l != 1 || (d.OH != 2 * d.IH && d.OH != 2 * d.IH - 1) || (d.OW != 2 * d.IW && d.OW != 2 * d.IW - 1)))
+            return INSV2V_EINVAL;
     } else if (d.mode != INSV2V_MODE_LINEAR) {
         return INSV2V_EUNSUPPORTED;
     }

@@ -105,7 +105,7 @@ __global__ __launch_bounds__(512) void gemm_q8_kernel(insv2v_gemm_desc p) {
     unsigned aoff[4];       // byte offset of this lane's 16 bytes for the cursor's (tile, source, tap); OOB_OFFSET = zero fill
     unsigned woff[4];
     const int nk = p.K / BK;
-    const int IHu = p.upsample ? p.IH * 2 : p.IH, IWu = p.upsample ? p.IW * 2 : p.IW;
+    const int IHu = p.upsample ? p.OH : p.IH, IWu = p.upsample ? p.OW : p.IW;   // upsample: the (possibly cropped) nearest-x2 image IS the output extent (stride 1, pad 1)
     const int ups = p.upsample ? 1 : 0;
     struct Cursor { int v, kt, k0, kh, kw, ci0, soffA; bool second; unsigned wbase; } cur = {(int)blockIdx.x, 0, 0, 0, 0, 0, 0, false, 0u};  // wave-uniform
     auto refresh_aoff = [&]() {

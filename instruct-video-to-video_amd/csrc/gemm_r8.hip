@@ -137,7 +137,7 @@ __global__ __launch_bounds__(512) void gemm_r8_kernel(insv2v_gemm_desc p, int de
     unsigned amax = 0;      // linear: this lane's offset in the LAST row of the current A source (clamp)
     const unsigned wmax = (unsigned)(((int64_t)(p.N - 1) * p.ldw + chunk8) * 2);   // ... in the last row of W
     const int nk = p.K / BK;
-    const int IHu = p.upsample ? p.IH * 2 : p.IH, IWu = p.upsample ? p.IW * 2 : p.IW;
+    const int IHu = p.upsample ? p.OH : p.IH, IWu = p.upsample ? p.OW : p.IW;   // upsample: the (possibly cropped) nearest-x2 image IS the output extent (stride 1, pad 1)
     const int ups = p.upsample ? 1 : 0;
     struct Cursor { int v, kt, k0, kh, kw, ci0, soffA, abm0; bool second; int tap, dpix; unsigned wbase; } cur = {(int)blockIdx.x, 0, 0, 0, 0, 0, 0, 0, false, 0, 0, 0u};  // wave-uniform
     if (CIM) cur.dpix = -p.IW - 1;

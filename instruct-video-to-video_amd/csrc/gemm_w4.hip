@@ -96,7 +96,7 @@ __global__ __launch_bounds__(WM * WN * 64, WM * WN / 2) void gemm_w4_kernel(W4Ar
     int arow[NPA], aoh[NPA], aow[NPA];
     unsigned woff[NPW];
     const int nk = p.K / BK4;  // >= 2 (host check): a tile's park vectors are retired by the wait of its second K tile
-    const int IHu = p.upsample ? p.IH * 2 : p.IH, IWu = p.upsample ? p.IW * 2 : p.IW;
+    const int IHu = p.upsample ? p.OH : p.IH, IWu = p.upsample ? p.OW : p.IW;   // upsample: the (possibly cropped) nearest-x2 image IS the output extent (stride 1, pad 1)
     const int ups = p.upsample ? 1 : 0;
     struct Cursor { int v, kt, k0, kh, kw, ci0; } cur = {(int)blockIdx.x, 0, 0, 0, 0, 0};  // wave-uniform scalars
     auto set_stage_tile = [&](int v) {

@@ -639,8 +639,11 @@ extern "C" int insv2v_layernorm(const insv2v_layernorm_desc* dp, insv2v_stream_t
 }
 
 // ------------------------------------------------------------------------------ row softmax
+// PAD: only the first `valid` columns take part; columns [valid, cols) - the padding of a leading dimension rounded up to 8 - are never
+// read as values and are written as exact zeros, so that a following GEMM may contract over all `cols` columns.
+template <bool PAD>
 __global__ __launch_bounds__(256) void softmax_rows_kernel(const half_t* x, half_t* y, int64_t ldx, int64_t ldy,
-                                                           int cols, float scale) {
+                                                           int cols, int valid, float scale) {
     __shared__ float red[8];
     const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const half_t* xr = x + (int64_t)row * ldx;
@@ -650,7 +653,8 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(const half_t* x, half
     for (int ch = tid; ch < CC; ch += 256) {
         half8 v = *(const half8*)(xr + ch * 8);
 #pragma unroll
-        for (int e = 0; e < 8; ++e) mx = fmaxf(mx, (float)v[e]);
+        for (int e = 0; e < 8; ++e)
+            if (!PAD || ch * 8 + e < valid) mx = fmaxf(mx, (float)v[e]);
     }
     mx = wave_max(mx);
     if (lane == 0) red[wid] = mx;
@@ -661,7 +665,8 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(const half_t* x, half
     for (int ch = tid; ch < CC; ch += 256) {
         half8 v = *(const half8*)(xr + ch * 8);
 #pragma unroll
-        for (int e = 0; e < 8; ++e) sum += exp2f(((float)v[e] - mx) * c);
+        for (int e = 0; e < 8; ++e)
+            if (!PAD || ch * 8 + e < valid) sum += exp2f(((float)v[e] - mx) * c);
     }
     sum = wave_sum(sum);
     if (lane == 0) red[4 + wid] = sum;
@@ -671,7 +676,7 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(const half_t* x, half
         half8 v = *(const half8*)(xr + ch * 8);
         half8 o;
 #pragma unroll
-        for (int e = 0; e < 8; ++e) o[e] = (half_t)(exp2f(((float)v[e] - mx) * c) * inv);
+        for (int e = 0; e < 8; ++e) o[e] = (!PAD || ch * 8 + e < valid) ? (half_t)(exp2f(((float)v[e] - mx) * c) * inv) : (half_t)0.f;
         *(half8*)(yr + ch * 8) = o;
     }
 }
@@ -680,7 +685,16 @@ extern "C" int insv2v_softmax_rows(const void* x, void* y, int64_t ldx, int64_t 
                                    float scale, insv2v_stream_t stream) {
     if (!x || !y || rows <= 0 || cols <= 0 || (cols & 7) || (ldx & 7) || (ldy & 7)) return INSV2V_EINVAL;
     if (scale < 0.f) return INSV2V_EINVAL;  // max is taken before scaling
-    hipLaunchKernelGGL(softmax_rows_kernel, dim3(rows), dim3(256), 0, as_stream(stream), (const half_t*)x,
-                       (half_t*)y, ldx, ldy, cols, scale);
+    hipLaunchKernelGGL(softmax_rows_kernel<false>, dim3(rows), dim3(256), 0, as_stream(stream), (const half_t*)x,
+                       (half_t*)y, ldx, ldy, cols, cols, scale);
+    return launch_status();
+}
+
+extern "C" int insv2v_softmax_rows_padded(const void* x, void* y, int64_t ldx, int64_t ldy, int32_t rows, int32_t cols, int32_t valid,
+                                          float scale, insv2v_stream_t stream) {
+    if (!x || !y || rows <= 0 || cols <= 0 || (cols & 7) || (ldx & 7) || (ldy & 7) || ldx < cols || ldy < cols) return INSV2V_EINVAL;
+    if (valid <= 0 || valid > cols || scale < 0.f) return INSV2V_EINVAL;
+    hipLaunchKernelGGL(softmax_rows_kernel<true>, dim3(rows), dim3(256), 0, as_stream(stream), (const half_t*)x,
+                       (half_t*)y, ldx, ldy, cols, valid, scale);
     return launch_status();
 }

@@ -23,6 +23,9 @@ template <bool UP> __device__ __forceinline__ int lds_px(int sp) { return UP ? s
 
 // ---- input transform.  One workgroup = IPB consecutive images x one 64-channel slice; LDS holds those images' (normalised) pixels
 // [IPB][H*W][64] fp16.  Thread = (work item tid / 8, 8-channel chunk tid % 8).
+// Odd H / W: ceil(H/2) x ceil(W/2) tiles per image; the last tile row / column hangs over the image by one pixel, which reads as zero exactly
+// like the border above / left of the image (also under the GroupNorm fold: a padded pixel is never normalised), and the output transform
+// does not store the row / column that does not exist.
 // UP (Upsample3D's nearest x2 + 3x3 convolution, resnet.py:48-69, in one Winograd pass): the 4x4 patch of output tile (y, x) on the upsampled grid is
 // the low-resolution 3x3 neighbourhood with its centre row / column doubled, so B^T d B has a zero row and column (index 2): 9 of the 16 matrices
 // remain - one tile per LOW-resolution pixel, groups g = ci * 3 + cj over (i, j) in {0, 1, 3}^2: 4 x fewer MACs than the direct form.
@@ -35,12 +38,13 @@ __global__ __launch_bounds__(256) void wino_input_kernel(const half_t* __restric
     const int nb0 = (int)blockIdx.x * ipb, c0 = (int)blockIdx.y * 64;
     // band blockIdx.z of the image: tile rows [tr0, tr1); staged pixel rows [row0, row0 + nrows) (row0 may be -1: rows outside the image are
     // never staged and read as zero).  One band (band_tr = all tile rows): the whole image, ipb images per workgroup.
-    const int trows = UP ? H : H >> 1;
+    const int trows = UP ? H : (H + 1) >> 1;
     const int tr0 = (int)blockIdx.z * band_tr, tr1 = min(tr0 + band_tr, trows);
     const bool whole = band_tr >= trows;
     const int row0 = whole ? 0 : (UP ? tr0 - 1 : 2 * tr0 - 1);
     const int nrows = whole ? H : (UP ? (tr1 - tr0) + 2 : 2 * (tr1 - tr0) + 2);
     const int HW = H * W, SW = nrows * W;   // pixels of an image / staged pixels per image
+    const int SWs = UP ? SW : (SW + 1) & ~1;  // LDS slots per image: lds_px swaps within aligned pairs, so an odd count is rounded up
     const bool second = x2 != nullptr && c0 >= C1;
     const half_t* src = second ? x2 + (c0 - C1) + chunk * 8 : x + c0 + chunk * 8;
     const int64_t ld = second ? ldx2 : ldx;
@@ -62,7 +66,7 @@ __global__ __launch_bounds__(256) void wino_input_kernel(const half_t* __restric
                 v[e] = (half_t)f;
             }
         }
-        *(half8*)(smem + ((int64_t)img * SW + lds_px<UP>(sp)) * 128 + chunk * 16) = v;   // staged pixel (img, sp)
+        *(half8*)(smem + ((int64_t)img * SWs + lds_px<UP>(sp)) * 128 + chunk * 16) = v;   // staged pixel (img, sp)
     }
     __syncthreads();
     // phase 2: one 4x4 patch -> 16 (UP: 9) transformed values per channel; zero padding outside the image (applied AFTER the norm, like the conv's)
@@ -72,7 +76,7 @@ __global__ __launch_bounds__(256) void wino_input_kernel(const half_t* __restric
             const int img = it / bt, tb_ = it - img * bt;
             const int y = tr0 + tb_ / W, xx = tb_ - (tb_ / W) * W;
             const int t = y * W + xx;
-            const char* base = smem + (int64_t)img * SW * 128 + chunk * 16;
+            const char* base = smem + (int64_t)img * SWs * 128 + chunk * 16;
             float hz[3][3][8];   // [low row y-1, y, y+1][(x-1) - x, 2 x, x - (x+1)]
 #pragma unroll
             for (int r = 0; r < 3; ++r) {
@@ -111,13 +115,13 @@ __global__ __launch_bounds__(256) void wino_input_kernel(const half_t* __restric
         }
         return;
     }
-    const int th = H >> 1, tw = W >> 1, ntile = th * tw;
+    const int th = (H + 1) >> 1, tw = (W + 1) >> 1, ntile = th * tw;
     const int bt = (tr1 - tr0) * tw;   // tiles of this band per image
     for (int it = item0; it < nimg * bt; it += 32) {
         const int img = it / bt, tb_ = it - img * bt;
         const int ty = tr0 + tb_ / tw, tx = tb_ - (tb_ / tw) * tw;
         const int t = ty * tw + tx;
-        const char* base = smem + (int64_t)img * SW * 128 + chunk * 16;
+        const char* base = smem + (int64_t)img * SWs * 128 + chunk * 16;
         float hz[4][4][8];   // horizontal transform of the four patch rows
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
@@ -170,7 +174,7 @@ __global__ __launch_bounds__(256) void wino_output_kernel(const half_t* __restri
     const int ch = (int)(idx - tile * c8) * 8;
     // UP: one tile per low-resolution pixel (ty, tx) = (y, x) of the H x W input, 2x2 output pixels of the 2H x 2W image; 9 matrices, the
     // patch row / column 2 of M is zero
-    const int th = UP ? H : H >> 1, tw = UP ? W : W >> 1, ntile = th * tw;
+    const int th = UP ? H : (H + 1) >> 1, tw = UP ? W : (W + 1) >> 1, ntile = th * tw;
     const int OW = UP ? 2 * W : W, OH = UP ? 2 * H : H;
     const int nb = (int)(tile / ntile), t = (int)(tile - (int64_t)nb * ntile);
     const int ty = t / tw, tx = t - ty * tw;
@@ -219,6 +223,7 @@ __global__ __launch_bounds__(256) void wino_output_kernel(const half_t* __restri
     for (int i = 0; i < 2; ++i)
 #pragma unroll
         for (int jj = 0; jj < 2; ++jj) {
+            if (!UP && (2 * ty + i >= OH || 2 * tx + jj >= OW)) continue;   // odd H / W: the last tile row / column has one pixel row / column only
             const int64_t m = m00 + (int64_t)i * OW + jj;
             float v[8];
 #pragma unroll
@@ -242,20 +247,21 @@ extern "C" int insv2v_winograd_input(const insv2v_winograd_in_desc* dp, insv2v_s
     if (!dp) return INSV2V_EINVAL;
     const insv2v_winograd_in_desc& d = *dp;
     if (!d.x || !d.v || d.NB <= 0 || d.H <= 0 || d.W <= 0 || d.C <= 0) return INSV2V_EINVAL;
-    if ((!d.upsample && ((d.H & 1) || (d.W & 1))) || (d.C % 64) || (d.x2 && (d.C1 <= 0 || d.C1 >= d.C || (d.C1 % 64)))) return INSV2V_EUNSUPPORTED;
+    if ((d.C % 64) || (d.x2 && (d.C1 <= 0 || d.C1 >= d.C || (d.C1 % 64)))) return INSV2V_EUNSUPPORTED;
     if ((d.ldx & 7) || ((uintptr_t)d.x & 15) || ((uintptr_t)d.v & 15) || (d.x2 && ((d.ldx2 & 7) || ((uintptr_t)d.x2 & 15)))) return INSV2V_EINVAL;
     if (d.gn_ab && (d.gn_images_per_sample <= 0 || ((uintptr_t)d.gn_ab & 15))) return INSV2V_EINVAL;
-    const int HW = d.H * d.W, ntile = d.upsample ? HW : HW / 4;
+    const int HW = d.H * d.W, ntile = d.upsample ? HW : ((d.H + 1) / 2) * ((d.W + 1) / 2);
+    const int HWs = d.upsample ? HW : (HW + 1) & ~1;   // LDS slots of a whole image (see SWs in the kernel)
     const int64_t tiles = (int64_t)d.NB * ntile;
     if (d.v_group_rows < tiles) return INSV2V_EINVAL;
     // One image's 64-channel slice is staged in at most 64 KiB of LDS: whole images (several per workgroup when they are small) or, for
     // larger ones, bands of tile rows with a one-pixel halo above and below (grid z)
-    const int trows = d.upsample ? d.H : d.H / 2;
+    const int trows = d.upsample ? d.H : (d.H + 1) / 2;
     int band_tr = trows, ipb = 1;
-    if (HW * 128 <= 64 * 1024) {
+    if (HWs * 128 <= 64 * 1024) {
         ipb = 32 / ntile;                                   // at least one work item per 8-thread group
         if (ipb < 1) ipb = 1;
-        while (ipb > 1 && ipb * HW * 128 > 64 * 1024) --ipb;
+        while (ipb > 1 && ipb * HWs * 128 > 64 * 1024) --ipb;
     } else {
         const int max_rows = 64 * 1024 / (d.W * 128);       // staged pixel rows that fit
         band_tr = d.upsample ? max_rows - 2 : (max_rows - 2) / 2;
@@ -264,7 +270,8 @@ extern "C" int insv2v_winograd_input(const insv2v_winograd_in_desc* dp, insv2v_s
     const int nbands = (trows + band_tr - 1) / band_tr;
     const int srows = nbands == 1 ? d.H : (d.upsample ? band_tr + 2 : 2 * band_tr + 2);
     const dim3 grid((unsigned)((d.NB + ipb - 1) / ipb), (unsigned)(d.C / 64), (unsigned)nbands);
-    const size_t lds = (size_t)ipb * srows * d.W * 128;
+    const int slots = srows * d.W;
+    const size_t lds = (size_t)ipb * (d.upsample ? slots : (slots + 1) & ~1) * 128;
 #define WINO_IN(NORM, UP)                                                                                                                             \
     hipLaunchKernelGGL((wino_input_kernel<NORM, UP>), grid, dim3(256), lds, as_stream(stream), (const half_t*)d.x, (const half_t*)d.x2, d.gn_ab, (half_t*)d.v, \
                        d.ldx, d.ldx2, d.x2 ? d.C1 : d.C, d.C, d.NB, d.H, d.W, ipb, d.gn_ab ? d.gn_images_per_sample : 1, d.gn_ab ? d.gn_silu : 0, d.v_group_rows, band_tr)
@@ -278,11 +285,11 @@ extern "C" int insv2v_winograd_output(const insv2v_winograd_out_desc* dp, insv2v
     if (!dp) return INSV2V_EINVAL;
     const insv2v_winograd_out_desc& d = *dp;
     if (!d.m || !d.y || d.NB <= 0 || d.H <= 0 || d.W <= 0 || d.Cout <= 0) return INSV2V_EINVAL;
-    if ((!d.upsample && ((d.H & 1) || (d.W & 1))) || (d.Cout & 7)) return INSV2V_EUNSUPPORTED;
+    if (d.Cout & 7) return INSV2V_EUNSUPPORTED;
     if ((d.ldy & 7) || ((uintptr_t)d.m & 15) || ((uintptr_t)d.y & 15) || (d.residual && ((d.ldr & 7) || ((uintptr_t)d.residual & 15)))) return INSV2V_EINVAL;
     if ((d.bias && ((uintptr_t)d.bias & 15)) || (d.row_bias && (((uintptr_t)d.row_bias & 15) || (d.ld_rb & 3) || d.rows_per_group <= 0 || d.rows_per_group % (d.H * d.W * (d.upsample ? 4 : 1)))))
         return INSV2V_EINVAL;
-    const int64_t tiles = d.upsample ? (int64_t)d.NB * d.H * d.W : (int64_t)d.NB * (d.H / 2) * (d.W / 2);
+    const int64_t tiles = d.upsample ? (int64_t)d.NB * d.H * d.W : (int64_t)d.NB * ((d.H + 1) / 2) * ((d.W + 1) / 2);
     if (d.m_group_rows < tiles) return INSV2V_EINVAL;
     const int64_t n = tiles * (d.Cout / 8);
     const dim3 grid((unsigned)((n + 255) / 256));

@@ -10,7 +10,7 @@ import os
 
 import torch  # noqa: F401  (must be imported first, see module docstring)
 
-ABI_VERSION = 12
+ABI_VERSION = 13
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("INSV2V_LIB", os.path.join(_HERE, "libinsv2v_hip.so"))  # override: A/B builds only
 
@@ -136,6 +136,7 @@ SIGNATURES = {
     "insv2v_attention": (c_i32, [C.POINTER(AttentionDesc), c_p]),
     "insv2v_embed_tokens": (c_i32, [c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_p]),
     "insv2v_softmax_rows": (c_i32, [c_p, c_p, c_i64, c_i64, c_i32, c_i32, c_f32, c_p]),
+    "insv2v_softmax_rows_padded": (c_i32, [c_p, c_p, c_i64, c_i64, c_i32, c_i32, c_i32, c_f32, c_p]),
     "insv2v_timestep_embedding": (c_i32, [c_p, c_p, c_i32, c_i32, c_f32, c_p]),
     "insv2v_build_unet_input": (c_i32, [c_p, c_p, c_p, c_p, c_f32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i64, c_i32, c_p]),
     "insv2v_cfg_step": (c_i32, [C.POINTER(StepDesc), c_p]),

@@ -357,8 +357,12 @@ def xattn_attn(x, wstream, kvstream, rows_per_sample, heads, ctx_len, eps=1e-5, 
     return out
 
 
-def _conv_geometry(geom, stride, pad, upsample):
+def _conv_geometry(geom, stride, pad, upsample, out_size=None):
     NB, IH, IW = geom
+    if out_size is not None:   # nearest-x2 upsample to an explicit size: the library checks OH in {2 IH - 1, 2 IH} (and OW alike)
+        if not upsample:
+            raise ValueError("conv3x3: out_size is the target of the nearest-x2 upsample (upsample=True)")
+        return int(out_size[0]), int(out_size[1])
     IHu, IWu = (IH * 2, IW * 2) if upsample else (IH, IW)
     pt, pl = pad
     # PyTorch conv arithmetic; the VAE's asymmetric (0,1,0,1) pad is pad=(0,0) with one extra row/col
@@ -428,9 +432,12 @@ def conv3x3_fuses_groupnorm(geom, cin, cout, k_split=0):
 
 
 def conv3x3(x, geom, w, bias=None, *, x2=None, stride=1, pad=(1, 1), upsample=False, residual=None, row_bias=None,
-            rows_per_group=0, out_fp32=False, tile=0, split_k=0, gn_ab=None, gn_images_per_sample=0, gn_silu=False, out=None, act=ACT_NONE):
+            rows_per_group=0, out_fp32=False, tile=0, split_k=0, gn_ab=None, gn_images_per_sample=0, gn_silu=False, out=None, act=ACT_NONE,
+            out_size=None):
     """3x3 convolution over channels-last pixels.  x: [NB*IH*IW, C1] (+x2 [.., C2]); w: [N, 9*(C1+C2)];
     geom = (NB, IH, IW).  Returns ([NB*OH*OW, N], (NB, OH, OW)).
+    out_size = (OH, OW) with upsample=True: the nearest-x2 image is taken WITHOUT its last row where OH = 2 IH - 1 (column: OW = 2 IW - 1) -
+    F.interpolate(size=out_size, mode="nearest"), Upsample3D's output_size - and zero-padded at that edge; None: exactly x2.
     gn_ab ([nsamples, C1+C2, 2] fp32 from groupnorm_stats): x is the RAW tensor and the kernel applies
     act(x*scale + shift) to its input on the fly (only where conv3x3_fuses_groupnorm says so).
     An input beyond the 2 GiB descriptor window of the kernels' LDS-DMA loads (the normalised [1 474 560, 960] concatenation entering
@@ -440,7 +447,7 @@ def conv3x3(x, geom, w, bias=None, *, x2=None, stride=1, pad=(1, 1), upsample=Fa
     _req(x, torch.float16, "conv.x"), _req(w, torch.float16, "conv.w")
     NB, IH, IW = geom
     pt, pl = pad
-    OH, OW = _conv_geometry(geom, stride, pad, upsample)
+    OH, OW = _conv_geometry(geom, stride, pad, upsample, out_size)
     N = w.shape[0]
     cin = x.shape[1] + (x2.shape[1] if x2 is not None else 0)
     M = NB * OH * OW
@@ -489,11 +496,15 @@ def winograd_weights(w, device, upsample=False):
     return u.reshape(-1, w.shape[0], w.shape[1]).to(device=device, dtype=torch.float16).contiguous()
 
 
-def winograd_ok(geom, cin, c1=0, upsample=False):
-    """Shapes insv2v_winograd_input accepts (else the caller uses conv3x3): even H, W (any with upsample: one tile per input pixel); image
-    rows of at most 128 pixels (an image's 64-channel slice is staged in LDS whole or in bands of tile rows)."""
+def winograd_ok(geom, cin, c1=0, upsample=False, out_size=None):
+    """Shapes insv2v_winograd_input accepts (else the caller uses conv3x3): any H, W (odd sizes: the last tile row / column hangs over the
+    image, reads zeros there and stores only the pixels that exist); image rows of at most 128 pixels (an image's 64-channel slice is staged
+    in LDS whole or in bands of tile rows).  upsample: one tile per input pixel, exact x2 only - the 9-tap form rests on the patch's two
+    centre rows / columns being equal, which a cropped target (out_size != (2 H, 2 W)) breaks at its zero-padded edge."""
     _, H, W = geom
-    return (upsample or (H % 2 == 0 and W % 2 == 0)) and W <= 128 and cin % 64 == 0 and c1 % 64 == 0
+    if upsample and out_size is not None and tuple(out_size) != (2 * H, 2 * W):
+        return False
+    return W <= 128 and cin % 64 == 0 and c1 % 64 == 0
 
 
 def winograd_conv3x3(x, geom, U, bias=None, *, x2=None, gn_ab=None, gn_images_per_sample=0, gn_silu=False, row_bias=None, rows_per_group=0,
@@ -509,7 +520,7 @@ def winograd_conv3x3(x, geom, U, bias=None, *, x2=None, gn_ab=None, gn_images_pe
     ng = 9 if upsample else 16                     # transformed taps that are not identically zero
     OH, OW = (2 * H, 2 * W) if upsample else (H, W)
     assert U.shape[0] == ng and U.shape[2] == C and x.shape[0] == NB * H * W
-    tiles = NB * H * W if upsample else NB * (H // 2) * (W // 2)
+    tiles = NB * H * W if upsample else NB * ((H + 1) // 2) * ((W + 1) // 2)   # odd H / W: the last tile row / column is half outside
     grows = -(-tiles // 256) * 256
     v = torch.empty((ng * grows, C), device=x.device, dtype=torch.float16)
     di = WinogradInDesc()
@@ -665,10 +676,15 @@ def embed_tokens(ids, tok, pos):
     return out
 
 
-def softmax_rows(x, scale=1.0):
+def softmax_rows(x, scale=1.0, valid=None):
+    """In-place row softmax of the last dimension; valid < x.shape[-1]: over the first `valid` columns, the others become exact zeros."""
     lib = _lib.load()
     _req(x, torch.float16, "softmax.x")
     x2 = x.reshape(-1, x.shape[-1])
+    if valid is not None and valid != x2.shape[1]:
+        check(lib.insv2v_softmax_rows_padded(x2.data_ptr(), x2.data_ptr(), x2.stride(0), x2.stride(0), x2.shape[0], x2.shape[1], valid,
+                                             scale, _stream()), "insv2v_softmax_rows_padded")
+        return x
     check(lib.insv2v_softmax_rows(x2.data_ptr(), x2.data_ptr(), x2.stride(0), x2.stride(0), x2.shape[0], x2.shape[1],
                                   scale, _stream()), "insv2v_softmax_rows")
     return x

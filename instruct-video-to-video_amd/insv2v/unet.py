@@ -546,6 +546,20 @@ class MotionModule:
         return x.like(ops.gemm(h, *self.proj_out, residual=x.t))
 
 
+def plan_sizes(H, W, levels=4):
+    """Spatial sizes of a latent through the UNet: ``down`` = the (h, w) of every level (each stride-2, pad-1 Downsample3D gives
+    ceil(h / 2)), ``up`` = the size every upsampler has to produce - the size of the skip tensor the next up block concatenates with,
+    i.e. the finer level's own size (the reference's upsample_size, unet.py:323-331,409-424): 2 h or 2 h - 1 per side.
+    A side below one pixel is refused."""
+    if H < 1 or W < 1 or levels < 1:
+        raise ValueError(f"UNet3DConditionModel: a latent of {H}x{W} pixels has a side that reaches 0")
+    down = [(int(H), int(W))]
+    for _ in range(levels - 1):
+        h, w = down[-1]
+        down.append(((h - 1) // 2 + 1, (w - 1) // 2 + 1))
+    return dict(down=down, up=down[-2::-1])
+
+
 class UNetOutput:
     def __init__(self, sample):
         self.sample = sample
@@ -672,6 +686,7 @@ class UNet3DConditionModel:
         x_in and t: everything in front of the first text cross-attention (the first ResnetBlock3D and the first spatial
         self-attention) is computed once for the two and copied (DEDUP_CFG)."""
         c = self.cfg
+        plan_sizes(H, W, len(c["ch"]))   # (refuses a degenerate latent; any other size runs: the upsamplers follow their skips' sizes)
         emb = ops.timestep_embedding(t_dev, c["ch"][0], c["shift"])
         emb = ops.gemm(emb, *self.te1, act=ops.ACT_SILU)
         semb = ops.gemm(emb, *self.te2, act=ops.ACT_SILU)  # silu(emb): the only form the resnets consume
@@ -718,10 +733,13 @@ class UNet3DConditionModel:
                 if m is not None:
                     x = m(x, start)
             if blk["up"] is not None:
-                if blk.get("up_u") is not None and x.t.shape[0] >= WINOGRAD_MIN_ROWS // 4 and ops.winograd_ok((B * F, x.H, x.W), x.t.shape[1], upsample=True):
+                # Upsample3D to the size of the skip the next block meets (the reference's upsample_size): 2 h, or 2 h - 1 where the
+                # stride-2 convolution on the way down rounded an odd side up; nearest to 2 h - 1 is the x2 image without its last row
+                tgt = (skips[-1].H, skips[-1].W)
+                if blk.get("up_u") is not None and x.t.shape[0] >= WINOGRAD_MIN_ROWS // 4 and ops.winograd_ok((B * F, x.H, x.W), x.t.shape[1], upsample=True, out_size=tgt):
                     t, oh, ow = ops.winograd_conv3x3(x.t, (B * F, x.H, x.W), blk["up_u"], blk["up"][1], upsample=True), 2 * x.H, 2 * x.W
                 else:
-                    t, (_, oh, ow) = ops.conv3x3(x.t, (B * F, x.H, x.W), *blk["up"], upsample=True)
+                    t, (_, oh, ow) = ops.conv3x3(x.t, (B * F, x.H, x.W), *blk["up"], upsample=True, out_size=None if tgt == (2 * x.H, 2 * x.W) else tgt)
                 x = x.like(t, oh, ow)
         n = ops.groupnorm(x.t, B, F * x.hw, *self.norm_out, c["groups"], c["eps"], silu=True)
         if NARROW_CONV_OUT and n.shape[0] >= NARROW_CONV_MIN_ROWS:
@@ -735,8 +753,6 @@ class UNet3DConditionModel:
         if not self.loaded:
             raise RuntimeError("UNet3DConditionModel: load_state_dict() has not been called")
         B, Cin, F, H, W = sample.shape
-        if any(s % 8 for s in (H, W)):
-            raise NotImplementedError("latent height/width must be multiples of 8 (three stride-2 stages)")
         dev = self.device
         x = sample.to(device=dev, dtype=torch.float32).permute(0, 2, 1, 3, 4).reshape(B * F, Cin, H, W)
         x_in = ops.nchw_to_nhwc_f16(x, self.in_pad)

@@ -44,21 +44,23 @@ class VAttn:
     def __call__(self, x, geom):
         N, H, W = geom
         C, HW = self.ch, H * W
-        if HW % 8:
-            raise NotImplementedError("VAE attention needs h*w to be a multiple of 8")
+        # The batched GEMMs want 16-byte leading dimensions (ldc = HW of the scores, K = HW of P.v): for an h*w that is not a multiple of 8
+        # the score rows and v^T rows are padded to HWp columns.  The softmax writes the pad columns of P as exact zeros and v^T's pad
+        # columns are zero, so contracting over HWp adds nothing.  HW % 8 == 0: HWp = HW, the launches of before.
+        HWp = (HW + 7) // 8 * 8
         n = ops.groupnorm(x, N, HW, *self.norm, GROUPS, EPS)
         qk = ops.gemm(n, self.wqk, self.bqk)  # [N*HW, 2C]
-        s = torch.empty((N, HW, HW), device=x.device, dtype=torch.float16)
+        s = torch.empty((N, HW, HWp), device=x.device, dtype=torch.float16)
         # S_f = q_f k_f^T * C^-0.5 (alpha applied in the epilogue keeps fp16 in range)
-        ops.gemm(qk, qk[:, C:], out=s, alpha=float(C) ** -0.5, batch=N, M=HW, N=HW, K=C, lda=2 * C, ldw=2 * C, ldc=HW,
-                 a_bs=HW * 2 * C, w_bs=HW * 2 * C, c_bs=HW * HW)
-        ops.softmax_rows(s)
+        ops.gemm(qk, qk[:, C:], out=s, alpha=float(C) ** -0.5, batch=N, M=HW, N=HW, K=C, lda=2 * C, ldw=2 * C, ldc=HWp,
+                 a_bs=HW * 2 * C, w_bs=HW * 2 * C, c_bs=HW * HWp)
+        ops.softmax_rows(s, valid=HW)
         # v^T_f [C, HW] = Wv n_f^T ; the v bias is added after P.v (softmax rows sum to 1)
-        vt = torch.empty((N, C, HW), device=x.device, dtype=torch.float16)
-        ops.gemm(self.wv, n, out=vt, batch=N, M=C, N=HW, K=C, lda=C, ldw=C, ldc=HW, a_bs=0, w_bs=HW * C, c_bs=C * HW)
+        vt = (torch.empty if HWp == HW else torch.zeros)((N, C, HWp), device=x.device, dtype=torch.float16)
+        ops.gemm(self.wv, n, out=vt, batch=N, M=C, N=HW, K=C, lda=C, ldw=C, ldc=HWp, a_bs=0, w_bs=HW * C, c_bs=C * HWp)
         o = torch.empty((N * HW, C), device=x.device, dtype=torch.float16)
-        ops.gemm(s.reshape(N * HW, HW), vt.reshape(N * C, HW), self.bv, out=o, batch=N, M=HW, N=C, K=HW, lda=HW, ldw=HW,
-                 ldc=C, a_bs=HW * HW, w_bs=C * HW, c_bs=HW * C)
+        ops.gemm(s.reshape(N * HW, HWp), vt.reshape(N * C, HWp), self.bv, out=o, batch=N, M=HW, N=C, K=HWp, lda=HWp, ldw=HWp,
+                 ldc=C, a_bs=HW * HWp, w_bs=C * HWp, c_bs=HW * C)
         return ops.gemm(o, *self.proj, residual=x)
 
 
@@ -126,6 +128,9 @@ class AutoencoderKL:
     def moments(self, x):
         """x [N,3,H,W] float -> channels-last fp32 moments [N*h*w, 2*embed_dim], (N,h,w)."""
         N, C, H, W = x.shape
+        down = 2 ** (len(self.dd["ch_mult"]) - 1)
+        if H % down or W % down:   # the (0,1,0,1)-padded stride-2 stages and the decoder's exact x2 (model.py:67-71,46-52) round-trip only these
+            raise ValueError(f"AutoencoderKL: image height and width must be multiples of {down}, got {H}x{W}")
         step = self._frames_per_call(H, W)
         if N > step:  # frames are independent: chunk so every operand fits the addressing window
             parts = [self.moments(x[i:i + step]) for i in range(0, N, step)]
