@@ -257,8 +257,9 @@ typedef struct insv2v_rowlin_desc {
     float stats_eps;
     /* gn_ab != NULL (plain form only: no layernorm / frame_bias / residual): a preceding GroupNorm is applied to x on the fly,
      * x <- x * scale + shift with [samples][K][2] fp32 (scale, shift) pairs from insv2v_groupnorm(stats_only); row m belongs to sample
-     * m / gn_rows (gn_rows % 32 == 0).  The transformer blocks' GroupNorm -> proj_in pair (attention.py:101-103, motion_module.py:136-139)
-     * without the normalised copy. */
+     * m / gn_rows.  Every gn_rows > 0 is accepted: each sample's rows are walked in 32-row wave blocks of its own (ceil(gn_rows / 32) per
+     * sample; the overhang of the last one reads zeros and is never stored), which for gn_rows % 32 == 0 is the plain tiling of the M rows.
+     * The transformer blocks' GroupNorm -> proj_in pair (attention.py:101-103, motion_module.py:136-139) without the normalised copy. */
     const float* gn_ab;
     int32_t gn_rows;
 } insv2v_rowlin_desc;
@@ -298,7 +299,9 @@ int64_t insv2v_tattn_attn_stream_elems(int32_t C, int32_t heads, int32_t frames)
  * Attention: to_q of the tokens, to_k / to_v of the text context, to_out[0]) for C = 320, 8 heads x 40, 64 < ctx_len <= 96:
  *     out = x + Wo . softmax_keys( (LayerNorm(x) Wq^T + Wq beta) K_b^T * scale ) V_b + bo,   b = row / rows_per_sample
  * replaces insv2v_rowlin (q) + insv2v_attention + insv2v_rowlin (out-proj, residual).  x / out: [M, C] fp16 (row strides ldx / ldo;
- * out must not alias x), rows_per_sample a multiple of 128, M a multiple of rows_per_sample.
+ * out must not alias x), M a multiple of rows_per_sample.  Every rows_per_sample > 0 is accepted: each sample's rows are walked in 128-row
+ * tiles of its own (ceil(rows_per_sample / 128) per sample; the overhang of the last one reads zeros and is never stored), which for
+ * rows_per_sample % 128 == 0 is the plain tiling of the M rows.  The same holds for insv2v_xattn_attn.
  * wstream: insv2v_xattn_stream_elems(C, heads, 0) halfs - q projection (LayerNorm gamma folded in, bias = Wq beta) and output
  * projection as MFMA fragments; kvstream: [M / rows_per_sample] x insv2v_xattn_stream_elems(C, heads, 1) halfs - the text K / V of each
  * sample as fragments, masked per head and zero beyond ctx_len (insv2v/fused.py pack_xattn_stream / pack_xattn_kv).  The K / V of the

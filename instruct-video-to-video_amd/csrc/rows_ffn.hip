@@ -264,6 +264,7 @@ struct RowLinArgs {
     float stats_eps;
     const float* gn_ab;           // GN: [samples][K][2] (scale, shift) of a preceding GroupNorm; sample = m / gn_rows
     int gn_rows;
+    int gn_units, gn_tiles;       // GN: 32-row wave blocks per sample = ceil(gn_rows / 32); 128-row tiles of the segmented schedule (insv2v_rowlin)
 };
 // stream per pass: per PAIR of 32-row output tiles (2p, 2p+1) one section of GP groups of 8 fragments (a whole number of 16-fragment slots):
 //   [for k-step s = 0..KS: (tile 2p, tile 2p+1)] = 2 (KS + 1) fragments, then padding;  s = KS is the bias step
@@ -291,6 +292,11 @@ template <int KS> struct LinCfg {
 // copies the 16 KS pairs (2.5 KiB at K = 320) of its 32 rows' sample once per tile - 3 loads per lane instead of 4 KS per lane from L2 - and
 // every lane reads its 8 channels per k-step from there (two distinct addresses per instruction: a broadcast).  `tab` = this wave's staging
 // area, tab_off = byte offset of the sample's table in rG (wave-uniform), or OOB.
+// The rows of this form follow a SEGMENTED schedule, so that a wave's 32 rows share one sample for every gn_rows: each sample gets
+// gn_units = ceil(gn_rows / 32) wave blocks of its own, wave block q = 4 tile + wave = (sample q / gn_units, unit q % gn_units) covers the real
+// rows sample * gn_rows + unit * 32 .. + 31, and the overhang of a sample's last block (rows at or beyond gn_rows) reads zeros and is never
+// stored.  One wave-uniform division per block, none per lane; the descriptors are based at the block's real first row.  With
+// gn_rows % 32 == 0 this is the plain tiling of the M rows.
 template <int KS>
 __device__ __forceinline__ void stage_gn_table(char* tab, srd_t rG, unsigned tab_off, int lane) {
     constexpr int BYTES = 16 * KS * 8;
@@ -329,7 +335,7 @@ __global__ __launch_bounds__(256, LinCfg<KS>::WGS) void rowlin_kernel(RowLinArgs
     const int tid = threadIdx.x, lane = tid & 63;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int tok = lane & 31, half = lane >> 5;
-    const int ntiles = (p.M + TROWS - 1) / TROWS;
+    const int ntiles = GN ? p.gn_tiles : (p.M + TROWS - 1) / TROWS;
     const int npairs = p.N >> 6;
     R ring;
     ring.init(smem, p.wstream, npairs * (GP / R::GPS), wid, lane);
@@ -359,22 +365,33 @@ __global__ __launch_bounds__(256, LinCfg<KS>::WGS) void rowlin_kernel(RowLinArgs
         half8 bstep[TB];
         // descriptors based at the tile's first row (64-bit), lane offsets relative to it: operands beyond 2 GiB (the fused q/k/v rows
         // of 20 stacked clips: [1 474 560, 960] fp16 = 2.8 GB) need no wider offsets
-        const int64_t trow0 = (int64_t)tile * TROWS;
+        int64_t trow0 = (int64_t)tile * TROWS;
+        int gn_sample = 0, gn_u0 = 0;   // GN: the wave block's sample and its first row inside the sample
+        if constexpr (GN) {              // (one token block per wave) the descriptors are the WAVE BLOCK's, based at its real first row
+            const int q = tile * 4 + wid;
+            gn_sample = __builtin_amdgcn_readfirstlane(q / p.gn_units);
+            gn_u0 = (q - gn_sample * p.gn_units) * 32;
+            trow0 = (int64_t)gn_sample * p.gn_rows + gn_u0;
+        }
         const srd_t rX = make_srd(p.x + trow0 * p.ldx), rO = make_srd(p.out + trow0 * p.ldo),
                     rR = make_srd(RES ? (const void*)(p.residual + trow0 * p.ldr) : (const void*)p.x);
 #pragma unroll
         for (int tb = 0; tb < TB; ++tb) {
-            const int ml = (wid * TB + tb) * 32 + tok;
-            m[tb] = tile * TROWS + ml;
-            mok[tb] = m[tb] < p.M;
+            const int ml = GN ? tok : (wid * TB + tb) * 32 + tok;
+            if constexpr (GN) {   // (a spare block of the last tile starts at or beyond M)
+                m[tb] = (int)trow0 + ml;
+                mok[tb] = gn_u0 + tok < p.gn_rows && trow0 + ml < p.M;
+            } else {
+                m[tb] = tile * TROWS + ml;
+                mok[tb] = m[tb] < p.M;
+            }
             xoff[tb] = mok[tb] ? (unsigned)(((int64_t)ml * p.ldx + 8 * half) * 2) : OOB_OFFSET;
             ooff[tb] = mok[tb] ? (unsigned)(((int64_t)ml * p.ldo + 8 * half) * 2) : OOB_OFFSET;
             roff[tb] = (RES && mok[tb]) ? (unsigned)(((int64_t)ml * p.ldr + 8 * half) * 2) : OOB_OFFSET;
             if constexpr (GN) {
-                // a wave's 32 rows share one sample (gn_rows % 32 == 0): its table goes through this wave's 16 KS * 8 bytes behind the ring
+                // a wave's 32 rows share one sample (the segmented schedule): its table goes through this wave's 16 KS * 8 bytes behind the ring
                 char* tab = smem + R::NS * R::SLOT_B + (wid * TB + tb) * (16 * KS * 8);
-                const int m0w = tile * TROWS + (wid * TB + tb) * 32;
-                const unsigned toff = m0w < p.M ? (unsigned)((int64_t)(m0w / p.gn_rows) * (16 * KS) * 8) : OOB_OFFSET;
+                const unsigned toff = trow0 < p.M ? (unsigned)((int64_t)gn_sample * (16 * KS) * 8) : OOB_OFFSET;
                 stage_gn_table<KS>(tab, make_srd(p.gn_ab), toff, lane);
                 request_rows<KS>(xf[tb], rX, xoff[tb]);
                 gn_apply_lds<KS>(xf[tb], tab, half);
@@ -497,7 +514,7 @@ static int launch_rowlin(const insv2v_rowlin_desc& d, const RowLinArgs& a, hipSt
     if (d.gn_ab) {   // fused input GroupNorm: only the plain form (proj_in of the transformer blocks) exists
         if (v != 0) return INSV2V_EUNSUPPORTED;
         static bool gn_attr = false;
-        return launch_rows((const void*)rowlin_kernel<KS, false, false, false, true>, gn_attr, lin_ring_slots<KS, true>() * LIN_SLOT_FR * 1024 + 4 * 16 * KS * 8, a, d.M, s, LinCfg<KS>::WGS);
+        return launch_rows((const void*)rowlin_kernel<KS, false, false, false, true>, gn_attr, lin_ring_slots<KS, true>() * LIN_SLOT_FR * 1024 + 4 * 16 * KS * 8, a, a.gn_tiles * 128, s, LinCfg<KS>::WGS);
     }
     if constexpr (KS == 40) {   // two token blocks per wave where the register file holds them: bit v of the mask (INSV2V_ROWLIN_TB2 overrides, for A/B)
         static const int tb2 = getenv("INSV2V_ROWLIN_TB2") ? atoi(getenv("INSV2V_ROWLIN_TB2")) : ROWLIN_TB2_DEFAULT;
@@ -526,9 +543,16 @@ extern "C" int insv2v_rowlin(const insv2v_rowlin_desc* dp, insv2v_stream_t strea
     // (descriptors are rebased per 128/256-row tile: only a tile's own extent has to fit the 2 GiB window, the operands may be larger)
     const int64_t lim = (int64_t)1 << 31;
     if (256 * (int64_t)d.ldx * 2 >= lim || 256 * (int64_t)d.ldo * 2 >= lim || (d.residual && 256 * (int64_t)d.ldr * 2 >= lim)) return INSV2V_EUNSUPPORTED;
-    const RowLinArgs a = {(const half_t*)d.x, (half_t*)d.out, (const half_t*)d.residual, (const half_t*)d.wstream, d.ldx, d.ldo, d.ldr,
-                          d.M, d.N, d.rows_per_frame, d.frames, d.eps, d.stats_out, d.stats_eps, d.gn_ab, d.gn_rows};
-    if (d.gn_ab && (d.gn_rows <= 0 || (d.gn_rows % 32) || ((uintptr_t)d.gn_ab & 15))) return INSV2V_EUNSUPPORTED;   // a wave's 32 rows share one sample
+    RowLinArgs a = {(const half_t*)d.x, (half_t*)d.out, (const half_t*)d.residual, (const half_t*)d.wstream, d.ldx, d.ldo, d.ldr,
+                    d.M, d.N, d.rows_per_frame, d.frames, d.eps, d.stats_out, d.stats_eps, d.gn_ab, d.gn_rows, 0, 0};
+    if (d.gn_ab) {
+        if (d.gn_rows <= 0 || ((uintptr_t)d.gn_ab & 15)) return INSV2V_EUNSUPPORTED;
+        // every sample (the last one may be partial) gets its own 32-row wave blocks, four of them to a tile
+        a.gn_units = (d.gn_rows + 31) / 32;
+        const int64_t blocks = ((int64_t)d.M + d.gn_rows - 1) / d.gn_rows * a.gn_units;
+        if ((blocks + 3) / 4 * 128 >= lim) return INSV2V_EUNSUPPORTED;
+        a.gn_tiles = (int)((blocks + 3) / 4);
+    }
     return d.K == 320 ? launch_rowlin<20>(d, a, as_stream(stream)) : launch_rowlin<40>(d, a, as_stream(stream));
 }
 

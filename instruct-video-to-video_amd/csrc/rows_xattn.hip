@@ -8,7 +8,8 @@ namespace {
 //     out = x + Wo . Attn( LayerNorm(x) Wq^T + Wq beta ;  K_b, V_b ) + bo          (b = the sample of the token row)
 // The text K / V of a sample are only 2 x 77 x 320 halfs and loop-invariant over the sampling loop, so they are a second WEIGHT STREAM:
 // insv2v/fused.py pack_xattn_kv lays them out per sample as MFMA A fragments, masked per head, in the order consumed here, and the
-// ring pulls them through LDS between the shared q-projection and output-projection weights (a 128-row tile lies inside one sample).
+// ring pulls them through LDS between the shared q-projection and output-projection weights.  A 128-row tile lies inside one sample for
+// every rows_per_sample - the segmented row schedule, XattnTile below.
 //   * q tiles ([32 channels] x [32 tokens], C layout) packed to fp16 are the B fragments of S^T = K_h . Q_h^T: a head is 40 channels = 5
 //     octets = two full k-steps + one half k-step whose other octet is ZERO IN THE K FRAGMENT (no masking in the kernel);
 //   * S^T is [96 keys] x [32 tokens] per head (3 accumulator tiles): softmax over the keys = in-lane over 48 values + one exchange with the
@@ -27,6 +28,23 @@ struct XattnArgs {
     float eps, scale;
     const half_t* pre_res;   // PRE: residual of the leading Linear (x is then the self-attention output), row stride ld_pre
     int64_t ld_pre;
+    int tiles_per_sample, ntiles;   // ceil(rows_per_sample / 128), samples * tiles_per_sample (xattn_args)
+};
+// The segmented row schedule of both text kernels: every sample gets ceil(rows_per_sample / 128) tiles of its own, so a tile never straddles
+// two samples' K / V streams whatever rows_per_sample is.  Tile t = (sample t / tiles_per_sample, unit t % tiles_per_sample) covers the real
+// rows sample * rows_per_sample + unit * 128 .. + 127; the overhang of a sample's last tile (rows at or beyond rows_per_sample) reads zeros
+// and is never stored (OOB offsets, as rows beyond M always were).  One wave-uniform division per tile, none per lane; with
+// rows_per_sample % 128 == 0 this is the plain tiling of the M rows.
+struct XattnTile {
+    int sample;   // wave-uniform
+    int m;        // this lane's token row
+    bool mok;     // ... is a real row of the sample
+    __device__ __forceinline__ XattnTile(const XattnArgs& p, int tile, int wid, int tok) {
+        sample = __builtin_amdgcn_readfirstlane(tile / p.tiles_per_sample);
+        const int ml = (tile - sample * p.tiles_per_sample) * 128 + wid * 32 + tok;
+        m = sample * p.rows_per_sample + ml;
+        mok = ml < p.rows_per_sample;
+    }
 };
 constexpr int XA_Q_FR = 224, XA_KV_FR = 176, XA_O_FR = 224, XA_TOTAL = XA_Q_FR + XA_KV_FR + XA_O_FR;
 constexpr int XA_QS = XA_Q_FR / 16, XA_KVS = XA_KV_FR / 16;
@@ -155,7 +173,7 @@ __global__ __launch_bounds__(256, 1) void xattn_fused_kernel(XattnArgs p) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int tok = lane & 31, half = lane >> 5;
-    const int ntiles = (p.M + 127) / 128;
+    const int ntiles = p.ntiles;
     const srd_t rX = make_srd(p.x), rO = make_srd(p.out), rH = make_srd(PRE ? (const void*)p.pre_res : (const void*)p.x);
     RingT ring;
     ring.init(smem, p.wstream, p.kvstream, wid, lane);
@@ -169,11 +187,12 @@ __global__ __launch_bounds__(256, 1) void xattn_fused_kernel(XattnArgs p) {
 
 #pragma unroll 1
     for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        const int m = tile * 128 + wid * 32 + tok;
-        const bool mok = m < p.M;
+        const XattnTile rt(p, tile, wid, tok);
+        const int m = rt.m;
+        const bool mok = rt.mok;
         const unsigned xoff = mok ? (unsigned)(((int64_t)m * p.ldx + 8 * half) * 2) : OOB_OFFSET;
         const unsigned ooff = mok ? (unsigned)(((int64_t)m * p.ldo + 8 * half) * 2) : OOB_OFFSET;
-        ring.kv_soff = __builtin_amdgcn_readfirstlane((tile * 128) / p.rows_per_sample) * (XA_KV_FR * 1024);
+        ring.kv_soff = rt.sample * (XA_KV_FR * 1024);
         const unsigned hoff = (PRE && mok) ? (unsigned)(((int64_t)m * p.ld_pre + 8 * half) * 2) : OOB_OFFSET;
         half8 xn[KS1];                     // PRE: first the self-attention output (operand of the leading Linear), then LayerNorm(x1)
         half8 x1[PRE ? KS1 : 1];           // PRE: x1 = leading Linear + residual, raw: the residual of the block's output
@@ -296,12 +315,14 @@ static int xattn_args(const insv2v_xattn_desc* dp, int C, int kv_fr, XattnArgs& 
     const insv2v_xattn_desc& d = *dp;
     if (!d.x || !d.out || !d.wstream || !d.kvstream || d.M <= 0 || d.rows_per_sample <= 0) return INSV2V_EINVAL;
     if (d.C != C || d.heads != 8 || d.ctx_len <= 64 || d.ctx_len > 96) return INSV2V_EUNSUPPORTED;
-    if ((d.rows_per_sample % 128) || (d.M % d.rows_per_sample)) return INSV2V_EUNSUPPORTED;   // a workgroup's 128 rows share one sample's K / V
+    if (d.M % d.rows_per_sample) return INSV2V_EUNSUPPORTED;   // whole samples: each gets its own 128-row tiles (XattnTile)
     if ((d.ldx & 7) || (d.ldo & 7) || ((uintptr_t)d.x & 15) || ((uintptr_t)d.out & 15) || ((uintptr_t)d.wstream & 15) || ((uintptr_t)d.kvstream & 15)) return INSV2V_EINVAL;
     const int64_t lim = (int64_t)1 << 31;
     if ((int64_t)d.M * d.ldx * 2 >= lim || (int64_t)d.M * d.ldo * 2 >= lim || (int64_t)(d.M / d.rows_per_sample) * kv_fr * 1024 >= lim) return INSV2V_EUNSUPPORTED;
     a = {(const half_t*)d.x, (half_t*)d.out, (const half_t*)d.wstream, (const half_t*)d.kvstream, d.ldx, d.ldo, d.M, d.rows_per_sample,
-         d.ctx_len, d.eps, d.scale, nullptr, 0};
+         d.ctx_len, d.eps, d.scale, nullptr, 0, 0, 0};
+    a.tiles_per_sample = (d.rows_per_sample + 127) / 128;
+    a.ntiles = (d.M / d.rows_per_sample) * a.tiles_per_sample;
     return 0;
 }
 
@@ -315,9 +336,9 @@ extern "C" int insv2v_xattn_fused(const insv2v_xattn_desc* dp, insv2v_stream_t s
         a.pre_res = (const half_t*)d.pre_residual;
         a.ld_pre = d.ld_pre;
         static bool pre_attr = false;
-        return launch_rows((const void*)xattn_fused_kernel<true>, pre_attr, KvRing::NS * KvRing::SLOT_B, a, d.M, as_stream(stream));
+        return launch_rows((const void*)xattn_fused_kernel<true>, pre_attr, KvRing::NS * KvRing::SLOT_B, a, a.ntiles * 128, as_stream(stream));
     }
-    return launch_rows((const void*)xattn_fused_kernel<false>, attr_set, KvRing::NS * KvRing::SLOT_B, a, d.M, as_stream(stream));
+    return launch_rows((const void*)xattn_fused_kernel<false>, attr_set, KvRing::NS * KvRing::SLOT_B, a, a.ntiles * 128, as_stream(stream));
 }
 
 // fp16 elements of the shared weight stream (q + output projections) and of ONE sample's K / V stream; 0 if unsupported
@@ -370,7 +391,7 @@ __global__ __launch_bounds__(256, 1) void xattn640_kernel(XattnArgs p) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int tok = lane & 31, half = lane >> 5;
-    const int ntiles = (p.M + 127) / 128;
+    const int ntiles = p.ntiles;
     const srd_t rX = make_srd(p.x), rO = make_srd(p.out);
     XbRing ring;
     ring.init(smem, p.wstream, p.kvstream, wid, lane);
@@ -383,11 +404,12 @@ __global__ __launch_bounds__(256, 1) void xattn640_kernel(XattnArgs p) {
 
 #pragma unroll 1
     for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        const int m = tile * 128 + wid * 32 + tok;
-        const bool mok = m < p.M;
+        const XattnTile rt(p, tile, wid, tok);
+        const int m = rt.m;
+        const bool mok = rt.mok;
         const unsigned xoff = mok ? (unsigned)(((int64_t)m * p.ldx + 8 * half) * 2) : OOB_OFFSET;
         const unsigned ooff = mok ? (unsigned)(((int64_t)m * p.ldo + 8 * half) * 2) : OOB_OFFSET;
-        ring.kv_soff = __builtin_amdgcn_readfirstlane((tile * 128) / p.rows_per_sample) * (4 * XB_KV_FR * 1024);
+        ring.kv_soff = rt.sample * (4 * XB_KV_FR * 1024);
         half8 xn[KS];
         load_rows<KS, true>(xn, rX, xoff, p.eps);
 
@@ -463,7 +485,7 @@ extern "C" int insv2v_xattn_attn(const insv2v_xattn_desc* dp, insv2v_stream_t st
     XattnArgs a;
     if (const int st = xattn_args(dp, 640, 4 * XB_KV_FR, a)) return st;
     static bool attr_set = false;
-    return launch_rows((const void*)xattn640_kernel, attr_set, KvRing::NS * KvRing::SLOT_B, a, dp->M, as_stream(stream));
+    return launch_rows((const void*)xattn640_kernel, attr_set, KvRing::NS * KvRing::SLOT_B, a, a.ntiles * 128, as_stream(stream));
 }
 
 // fp16 elements of the q weight stream / of ONE sample's K / V stream of insv2v_xattn_attn; 0 if unsupported

@@ -372,3 +372,22 @@ def pack_xattn640_kv(kv, samples, ctx_len, C, heads):
     """kv [samples * ctx_len, 2C] fp16 -> [samples, 4 * XB_KV_FR * 512] fragment streams of insv2v_xattn_attn (one gather)."""
     flat = torch.cat([kv.reshape(samples, ctx_len * 2 * C), kv.new_zeros((samples, 1))], dim=1)
     return flat.index_select(1, xattn640_kv_index(C, heads, ctx_len, kv.device)).contiguous()
+
+
+def row_units(M, seg_rows, unit):
+    """The segmented row schedule of the kernels whose work unit must stay inside one segment of the token rows: the text cross-attention
+    kernels (segment = a sample's rows_per_sample rows, unit = a 128-row tile: one K / V stream per tile) and the GroupNorm fold of
+    insv2v_rowlin (segment = the gn_rows rows of one (sample, frame) group, unit = a wave's 32 rows: one (scale, shift) table per wave).
+    Every segment gets ceil(seg_rows / unit) units of its own; the overhang of its last unit reads zeros and is never stored.
+    -> (units_per_segment, n_units).  With seg_rows % unit == 0 this is the plain tiling: n_units == M // unit."""
+    if M <= 0 or seg_rows <= 0 or unit <= 0 or M % seg_rows:
+        raise ValueError(f"row_units: {M} rows are not whole segments of {seg_rows}")
+    ups = -(-seg_rows // unit)
+    return ups, (M // seg_rows) * ups
+
+
+def unit_rows(q, seg_rows, unit):
+    """Unit q of the schedule of row_units -> (segment, first real row, number of real rows)."""
+    ups = -(-seg_rows // unit)
+    s, u = divmod(q, ups)
+    return s, s * seg_rows + u * unit, min(unit, seg_rows - u * unit)

@@ -227,7 +227,9 @@ def rowlin_supported(N, K):
 def rowlin(x, wstream, N, *, layernorm=False, residual=None, frames=0, rows_per_frame=0, eps=1e-5, out=None, emit_stats=False, stats_eps=1e-5,
            gn_ab=None, gn_rows=0):
     """out = [LayerNorm](x) W^T + bias [+ residual] on the register-resident kernel (insv2v_rowlin); wstream from
-    fused.pack_linear_stream (frames > 0: it carries a per-frame bias table and row m uses frame (m // rows_per_frame) % frames)."""
+    fused.pack_linear_stream (frames > 0: it carries a per-frame bias table and row m uses frame (m // rows_per_frame) % frames).
+    gn_ab (groupnorm_stats) with gn_rows: the GroupNorm of row m's sample m // gn_rows is applied to x on the fly; every gn_rows > 0
+    (a sample's rows go in 32-row wave blocks of its own, fused.row_units)."""
     lib = _lib.load()
     _req(x, torch.float16, "rowlin.x"), _req(wstream, torch.float16, "rowlin.wstream")
     M, K = x.shape
@@ -303,8 +305,9 @@ def tattn_attn(x, wstream, samples, HW, heads, frames, eps=1e-5, out=None):
 
 
 def xattn_fused_supported(C, heads, ctx_len, rows_per_sample):
-    """True if insv2v_xattn_fused handles this text cross-attention block (C = 320, 8 heads, 64 < ctx_len <= 96, samples in 128-row tiles)."""
-    return int(_lib.load().insv2v_xattn_stream_elems(C, heads, 0)) > 0 and 64 < ctx_len <= 96 and rows_per_sample % 128 == 0
+    """True if insv2v_xattn_fused handles this text cross-attention block (C = 320, 8 heads, 64 < ctx_len <= 96; every rows_per_sample:
+    a sample's rows go in 128-row tiles of its own, fused.row_units)."""
+    return int(_lib.load().insv2v_xattn_stream_elems(C, heads, 0)) > 0 and 64 < ctx_len <= 96 and rows_per_sample > 0
 
 
 def xattn_fused(x, wstream, kvstream, rows_per_sample, heads, ctx_len, eps=1e-5, out=None, pre_residual=None):
@@ -333,8 +336,9 @@ def xattn_fused(x, wstream, kvstream, rows_per_sample, heads, ctx_len, eps=1e-5,
 
 
 def xattn_attn_supported(C, heads, ctx_len, rows_per_sample):
-    """True if insv2v_xattn_attn handles this text cross-attention (C = 640, 8 heads, 64 < ctx_len <= 96, samples in 128-row tiles)."""
-    return int(_lib.load().insv2v_xattn_attn_stream_elems(C, heads, 0)) > 0 and 64 < ctx_len <= 96 and rows_per_sample % 128 == 0
+    """True if insv2v_xattn_attn handles this text cross-attention (C = 640, 8 heads, 64 < ctx_len <= 96; every rows_per_sample:
+    a sample's rows go in 128-row tiles of its own, fused.row_units)."""
+    return int(_lib.load().insv2v_xattn_attn_stream_elems(C, heads, 0)) > 0 and 64 < ctx_len <= 96 and rows_per_sample > 0
 
 
 def xattn_attn(x, wstream, kvstream, rows_per_sample, heads, ctx_len, eps=1e-5, out=None):

@@ -302,7 +302,7 @@ class SpatialTransformer:
         scale = hd ** -0.5
         rl = self.rl if (C != 640 or _rowlin_640_pays(x.t.shape[0])) else None
         a = None
-        if rl is not None and ROWLIN_GN and HW % 32 == 0 and shared > 0 and x.B == 3 * shared:
+        if rl is not None and ROWLIN_GN and shared > 0 and x.B == 3 * shared:
             r1, r2 = shared * x.F * HW, 2 * shared * x.F * HW
             ab = ops.groupnorm_stats(x.t[:r2], 2 * shared * x.F, HW, *self.norm, self.groups, 1e-6)
             h, st = torch.empty((x.t.shape[0], C), device=x.t.device, dtype=torch.float16), None
@@ -315,7 +315,7 @@ class SpatialTransformer:
                           q_addr=(1, HW * 3 * C, 0), kv_addr=(1, HW * 3 * C, 0), o_addr=(1, HW * C, 0))
             ops.copy_rows(h[r2:], h[r1:r2])
             ops.copy_rows(a[r2:], a[r1:r2])
-        elif rl is not None and ROWLIN_GN and HW % 32 == 0:
+        elif rl is not None and ROWLIN_GN:
             ab = ops.groupnorm_stats(x.t, BF, HW, *self.norm, self.groups, 1e-6)
             h, st = ops.rowlin(x.t, rl["proj_in"], C, gn_ab=ab, gn_rows=HW), None
             qkv = ops.rowlin(h, rl["qkv"], 3 * C, layernorm=True)
@@ -484,7 +484,7 @@ class MotionModule:
         fused_attn = win and FUSE_TATTN and ops.tattn_fused_supported(C, self.heads, F)
         fused_640 = win and FUSE_TATTN_640 and ops.tattn_attn_supported(C, self.heads, F)
         row_flow = rl_frames or fused_attn or fused_640   # no folded-LayerNorm q/k/v GEMM, so no LayerNorm statistics passes
-        if rl is not None and ROWLIN_GN and HW % 32 == 0:
+        if rl is not None and ROWLIN_GN:
             ab = ops.groupnorm_stats(x.t, x.B * F, HW, *self.norm, self.groups, 1e-6)
             h, st = ops.rowlin(x.t, rl["proj_in"], C, gn_ab=ab, gn_rows=HW), None
         elif rl is not None:

@@ -147,8 +147,9 @@ def case_blocks():
 
 
 def case_unet_full():
-    """Full width: a branch-major CFG triple of 16 frames at latent 9x8 (72 pixels: 16 * 72 rows per sample keep the fused text
-    cross-attention, 72 % 32 != 0 drops the GroupNorm fold of the row kernels; every upsampler crops its rows: 2 -> 3 -> 5 -> 9)."""
+    """Full width: a branch-major CFG triple of 16 frames at latent 9x8 (72 and 20 pixels per frame at the row-kernel levels: samples of 1152
+    and 320 rows in the fused text cross-attention's 128-row tiles, ragged 32-row wave blocks in the GroupNorm fold; every upsampler crops
+    its rows: 2 -> 3 -> 5 -> 9)."""
     from modules.video_unet_temporal.unet import UNet3DConditionModel as RefUNet
     unet = load_synth(RefUNet(**synth.UNET_FULL))
     lat = synth.synth_input("anysize.full.latent", (1, 4, 16, 9, 8))   # [b, c, f, h, w]
