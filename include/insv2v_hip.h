@@ -47,7 +47,9 @@ typedef void* insv2v_stream_t; /* hipStream_t */
 #define INSV2V_MODE_LINEAR 0
 #define INSV2V_MODE_CONV3X3 1
 
-/* ABI version, bumped on any struct change. */
+/* ABI version, bumped on any struct change.
+ * ABI 14: seeded noise - insv2v_randn, insv2v_posterior_sample_seeded and the noise_seed / noise_stream / noise_on fields of
+ * insv2v_step_desc (section "seeded noise" below holds the stream definition, which is part of this contract). */
 int insv2v_abi_version(void);
 /* One-time per-process setup (kernel attributes). Safe to call repeatedly. */
 int insv2v_init(void);
@@ -498,6 +500,11 @@ typedef struct insv2v_step_desc {
     float c_x0, c_eps, c_xt, c_noise;
     float guidance_rescale;
     int64_t branch_stride; /* fp32 elements of eps_in between consecutive branches; 0 = F*h*w*4 */
+    /* (ABI 14) noise == NULL, noise_on != 0 and c_noise != 0: the variance noise [F,4,h,w] is generated inside the kernel, element
+     * (flat index) i of it = element i of the normal stream (noise_seed, noise_stream) of the section "seeded noise" - bit-identical
+     * to insv2v_randn into a tensor passed as `noise`, without that tensor.  noise_on != 0 with a non-NULL noise: INSV2V_EINVAL. */
+    int64_t noise_seed, noise_stream;
+    int32_t noise_on;
 } insv2v_step_desc;
 int insv2v_cfg_step(const insv2v_step_desc* d, insv2v_stream_t stream);
 /* std over all elements of n1 (branch 1) and of the CFG-combined eps -> stats[0..1] (inference.py:18-19). */
@@ -532,6 +539,40 @@ int insv2v_nhwc_to_nchw_f32(const void* x, int32_t x_is_fp32, float* y, int32_t 
  * moments fp32 [N,H,W,8] channels-last (mean|logvar) + noise fp32 [N,4,H,W] -> z fp32 [N,4,H,W]. */
 int insv2v_posterior_sample(const float* moments, const float* noise, float* z, int32_t N, int32_t H,
                             int32_t W, int32_t ldm, float scale, insv2v_stream_t stream);
+/* (ABI 14) The same with the noise generated inside the kernel: element i of the [N,4,H,W] sample takes element offset + i of the normal
+ * stream (seed, stream) of the section "seeded noise".  offset = flat index of this call's first frame inside the video's [T,4,H,W], so
+ * a video encoded in several calls gets the sample of one call.  Bit-identical to insv2v_randn + insv2v_posterior_sample. */
+int insv2v_posterior_sample_seeded(const float* moments, float* z, int32_t N, int32_t H, int32_t W, int32_t ldm, float scale,
+                                   int64_t seed, int64_t stream, int64_t offset, insv2v_stream_t hip_stream);
+
+/*
+ * ---- seeded noise (ABI 14) -----------------------------------------------------------------------------------------------------------
+ * Every random draw of the sampling path (VAE posterior noise, initial latents, DDPM variance noise) can come from a counter-based
+ * generator, so that a value is a pure function of (seed, stream id, element index) - independent of call order, of how units are
+ * stacked or split, and of the number of GPUs.  The definition below is a PUBLIC CONTRACT: it does not change between versions (a
+ * checkpointed experiment must replay), and tests/philox_ref.py restates it in numpy.
+ *
+ *   generator   Philox4x32-10 (Salmon et al., SC'11; the Random123 known answers hold): multipliers 0xD2511F53 / 0xCD9E8D57, Weyl key
+ *               increments 0x9E3779B9 / 0xBB67AE85, ten rounds.
+ *   key         (seed & 0xffffffff, seed >> 32); seed is an int64_t taken as its two's-complement bits.
+ *   counter     (block & 0xffffffff, block >> 32, stream & 0xffffffff, stream >> 32), block = element index >> 2.
+ *   element i   output word i & 3 of block i >> 2: any sub-range can be generated on its own and is bit-identical to the same range
+ *               of a longer draw.
+ *   uniform     u = ((word >> 8) + 0.5) * 2^-24, strictly inside (0, 1).
+ *   normal      Box-Muller per pair of words of a block: z0 = r0 cos(2 pi u1), z1 = r0 sin(2 pi u1), r0 = sqrt(-2 ln u0); z2, z3 likewise
+ *               from u2, u3.  |z| <= 5.89.  The kernels evaluate this in fp32 from exact images of the words (csrc/rng.h); the error
+ *               against a float64 evaluation is recorded in DESIGN.md.
+ *   stream id   what the host packs per purpose (insv2v/rng.py stream_id(kind, unit, window, step)); the kernels take any int64_t:
+ *                 bits 52-53 kind (0 ENC, 1 INIT, 2 STEP) | bits 28-51 unit (< 2^24) | bits 16-27 window (< 2^12) | bits 0-15 step (< 2^16)
+ *               ENC : element index over the whole video's posterior noise [T,4,h,w] (window = step = 0);
+ *               INIT: element index over the NEW frames [n,4,h,w] of window k (the overlap re-uses the previous window's initial noise);
+ *               STEP: element index over the clip's [F,4,h,w] at window k, sampling step i.
+ *
+ * insv2v_randn writes elements [offset, offset + n) of the stream (seed, stream) to out: fp32 normals, or with raw = 1 the 32-bit words'
+ * bit patterns.  n and offset are 64-bit (offset + n may cross a multiple of 2^34, where the block index carries into its high word);
+ * out needs 4-byte alignment only.  n < 0, offset < 0, an index range beyond int64 or raw outside {0, 1}: INSV2V_EINVAL.
+ */
+int insv2v_randn(float* out, int64_t n, int64_t seed, int64_t stream, int64_t offset, int32_t raw, insv2v_stream_t hip_stream);
 
 /*
  * ---- optical-flow estimator (ABI 9) --------------------------------------------------------------------------------------------------

@@ -3,6 +3,7 @@
 // layout conversions.  Latents follow the reference layout [F,4,h,w] fp32 (they are
 // API-visible); UNet-side tensors are channels-last.
 #include "common.h"
+#include "rng.h"
 #include <atomic>
 #include <cstdio>
 
@@ -115,7 +116,9 @@ __global__ void cfg_step_kernel(insv2v_step_desc p, int do_step) {
         if (do_step) {
             float x0 = (xt - p.sqrt_1ma * e) / p.sqrt_a;
             float prev = p.c_x0 * x0 + p.c_eps * e + p.c_xt * xt;
+            // seeded (ABI 14): the variance noise is element li of (noise_seed, noise_stream), generated here - no tensor of it exists
             if (p.noise) prev += p.c_noise * p.noise[li];
+            else if (p.noise_on) prev += p.c_noise * rng_normal_at(p.noise_seed, p.noise_stream, li);
             if (p.pred_x0) p.pred_x0[li] = x0;
             p.latent_out[li] = prev;
         }
@@ -131,6 +134,8 @@ extern "C" int insv2v_cfg_step(const insv2v_step_desc* dp, insv2v_stream_t strea
     if (d.correct == 2 && !d.delta_q && d.R < d.F) return INSV2V_EINVAL;
     const int do_step = d.latent_out != nullptr;
     if (!do_step && !d.eps_out) return INSV2V_EINVAL;
+    if (d.noise_on && d.noise) return INSV2V_EINVAL;   // one source of variance noise: a tensor or the stream, never both
+    if (d.c_noise == 0.f) d.noise_on = 0;
     int64_t n = 4ll * d.h * d.w;
     hipLaunchKernelGGL(cfg_step_kernel, dim3((unsigned)((n + 127) / 128)), dim3(128), 0, as_stream(stream), d, do_step);
     return launch_status();
@@ -353,7 +358,9 @@ extern "C" int insv2v_nhwc_to_nchw_f32(const void* x, int32_t x_is_fp32, float* 
     hipLaunchKernelGGL(nhwc_to_nchw_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, as_stream(stream), x, x_is_fp32, y, N, C, H, W, ldx, scale);
     return launch_status();
 }
-__global__ void posterior_sample_kernel(const float* mom, const float* noise, float* z, int N, int H, int W, int ldm, float scale) {
+// noise == NULL: element i of the sample takes element offset + i of the normal stream (seed, stream) (insv2v_posterior_sample_seeded)
+__global__ void posterior_sample_kernel(const float* mom, const float* noise, float* z, int N, int H, int W, int ldm, float scale,
+                                        int64_t seed, int64_t stream, int64_t offset) {
     int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;  // over N*4*H*W
     int64_t hw = (int64_t)H * W;
     if (i >= (int64_t)N * 4 * hw) return;
@@ -362,13 +369,60 @@ __global__ void posterior_sample_kernel(const float* mom, const float* noise, fl
     int c = nc % 4, n = nc / 4;
     const float* m = mom + ((int64_t)n * hw + r) * ldm;
     float logvar = fminf(fmaxf(m[4 + c], -30.f), 20.f);
-    z[i] = (m[c] + expf(0.5f * logvar) * noise[i]) * scale;
+    const float nz = noise ? noise[i] : rng_normal_at(seed, stream, offset + i);
+    z[i] = (m[c] + expf(0.5f * logvar) * nz) * scale;
 }
 extern "C" int insv2v_posterior_sample(const float* moments, const float* noise, float* z, int32_t N, int32_t H,
                                        int32_t W, int32_t ldm, float scale, insv2v_stream_t stream) {
     if (!moments || !noise || !z || N <= 0 || ldm < 8) return INSV2V_EINVAL;
     int64_t n = (int64_t)N * 4 * H * W;
-    hipLaunchKernelGGL(posterior_sample_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, as_stream(stream), moments, noise, z, N, H, W, ldm, scale);
+    hipLaunchKernelGGL(posterior_sample_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, as_stream(stream), moments, noise, z, N, H, W, ldm, scale,
+                       (int64_t)0, (int64_t)0, (int64_t)0);
+    return launch_status();
+}
+extern "C" int insv2v_posterior_sample_seeded(const float* moments, float* z, int32_t N, int32_t H, int32_t W, int32_t ldm, float scale,
+                                              int64_t seed, int64_t stream, int64_t offset, insv2v_stream_t hip_stream) {
+    if (!moments || !z || N <= 0 || H <= 0 || W <= 0 || ldm < 8 || offset < 0) return INSV2V_EINVAL;
+    int64_t n = (int64_t)N * 4 * H * W;
+    if (offset > INT64_MAX - n) return INSV2V_EINVAL;
+    hipLaunchKernelGGL(posterior_sample_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, as_stream(hip_stream), moments, (const float*)nullptr, z,
+                       N, H, W, ldm, scale, seed, stream, offset);
+    return launch_status();
+}
+
+// ---- seeded noise (ABI 14): elements [offset, offset + n) of the stream (seed, stream), normals or (raw) the 32-bit words themselves.
+// One thread per Philox block = 4 consecutive elements, stored as one 16-byte vector where the whole block lies inside the range and
+// `vec` says that out + (4 block - offset) is 16-byte aligned; the head (offset & 3 != 0) and the tail store element by element.
+__global__ __launch_bounds__(256) void randn_kernel(float* out, int64_t n, int64_t seed, int64_t stream, int64_t offset, int64_t nblocks, int raw, int vec) {
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= nblocks) return;
+    const uint64_t block = ((uint64_t)offset >> 2) + (uint64_t)t;
+    const rng_words q = rng_philox_block(seed, stream, block);
+    float z[4];
+    if (raw) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) z[j] = __uint_as_float(q.w[j]);
+    } else {
+        rng_normal4(q, z);
+    }
+    const int64_t o = (int64_t)(block << 2) - offset;   // where element 0 of this block lands in out: -3 ... n - 1
+    if (vec && o >= 0 && o + 4 <= n) {
+        *(uint4*)(out + o) = make_uint4(__float_as_uint(z[0]), __float_as_uint(z[1]), __float_as_uint(z[2]), __float_as_uint(z[3]));
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (o + j >= 0 && o + j < n) ((uint32_t*)out)[o + j] = __float_as_uint(z[j]);
+    }
+}
+extern "C" int insv2v_randn(float* out, int64_t n, int64_t seed, int64_t stream, int64_t offset, int32_t raw, insv2v_stream_t hip_stream) {
+    if (!out || ((uintptr_t)out & 3) || n < 0 || offset < 0 || (raw != 0 && raw != 1)) return INSV2V_EINVAL;
+    if (offset > INT64_MAX - n - 3) return INSV2V_EINVAL;   // element indices are int64
+    if (n == 0) return INSV2V_OK;
+    const int64_t nblocks = ((offset + n + 3) >> 2) - (offset >> 2);
+    const int64_t grid = (nblocks + 255) / 256;
+    if (grid > 0x7fffffffll) return INSV2V_EINVAL;
+    const int vec = ((((uintptr_t)out >> 2) - (uint64_t)offset) & 3) == 0;
+    hipLaunchKernelGGL(randn_kernel, dim3((unsigned)grid), dim3(256), 0, as_stream(hip_stream), out, n, seed, stream, offset, nblocks, (int)raw, vec);
     return launch_status();
 }
 
@@ -405,7 +459,7 @@ extern "C" int insv2v_tap_gather(const float* y9, int64_t ld9, const float* bias
     return launch_status();
 }
 
-extern "C" int insv2v_abi_version(void) { return 13; }
+extern "C" int insv2v_abi_version(void) { return 14; }
 // The process's device (one process per GPU): latched once, by insv2v_init or by the first launcher that asks.
 static std::atomic<int> g_first_device{-1};
 bool insv2v_one_device_check() {

@@ -10,7 +10,7 @@ import os
 
 import torch  # noqa: F401  (must be imported first, see module docstring)
 
-ABI_VERSION = 13
+ABI_VERSION = 14
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("INSV2V_LIB", os.path.join(_HERE, "libinsv2v_hip.so"))  # override: A/B builds only
 
@@ -94,7 +94,7 @@ class StepDesc(C.Structure):
                 ("nbranch", c_i32), ("F", c_i32), ("h", c_i32), ("w", c_i32), ("R", c_i32), ("correct", c_i32),
                 ("text_cfg", c_f32), ("img_cfg", c_f32), ("sqrt_a", c_f32), ("sqrt_1ma", c_f32),
                 ("c_x0", c_f32), ("c_eps", c_f32), ("c_xt", c_f32), ("c_noise", c_f32), ("guidance_rescale", c_f32),
-                ("branch_stride", c_i64)]
+                ("branch_stride", c_i64), ("noise_seed", c_i64), ("noise_stream", c_i64), ("noise_on", c_i32)]
 
 
 class Im2colDesc(C.Structure):
@@ -148,6 +148,8 @@ SIGNATURES = {
     "insv2v_nchw_to_nhwc_f16": (c_i32, [c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_f32, c_p]),
     "insv2v_nhwc_to_nchw_f32": (c_i32, [c_p, c_i32, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_f32, c_p]),
     "insv2v_posterior_sample": (c_i32, [c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_f32, c_p]),
+    "insv2v_posterior_sample_seeded": (c_i32, [c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_f32, c_i64, c_i64, c_i64, c_p]),
+    "insv2v_randn": (c_i32, [c_p, c_i64, c_i64, c_i64, c_i64, c_i32, c_p]),
     "insv2v_im2col": (c_i32, [C.POINTER(Im2colDesc), c_p]),
     "insv2v_instance_norm": (c_i32, [c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i64, c_i64, c_i32, c_f32, c_i32, c_p]),
     "insv2v_ew": (c_i32, [c_i32, c_p, c_p, c_p, c_p, c_i64, c_i32, c_i64, c_i64, c_i64, c_i64, c_p]),

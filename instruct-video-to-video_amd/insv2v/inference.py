@@ -19,6 +19,7 @@ import weakref
 import torch
 
 from . import ops
+from .rng import stream_id, STEP
 from .schedulers import DDIMScheduler, DDPMScheduler
 from .flow_utils import resize_flow
 
@@ -246,6 +247,13 @@ def max_clips_in_flight(frames=16, h=32, w=48):
     return max(1, min(MAX_CLIPS_IN_FLIGHT, (2 ** 31 - 2 ** 20) // (3 * frames * h * w * 640 * 2)))
 
 
+def _rng_of(kw):
+    """(seed, unit, window) of a call's kwargs, or None without a seed."""
+    if kw.get("seed") is None:
+        return None
+    return (kw["seed"], kw.get("unit", 0), kw.get("window", 0))
+
+
 class InferenceIP2PVideo(Inference):
     def zeros(self, x):
         return torch.zeros_like(x)
@@ -286,9 +294,10 @@ class InferenceIP2PVideo(Inference):
             return done.value
 
     def _loop_gen(self, latent, text_cond, text_uncond, img_cond, text_cfg, img_cfg, start_time, guidance_rescale,
-                  latent_ref=None, noise_correct_step=0.0, flows=None, slot=0):
+                  latent_ref=None, noise_correct_step=0.0, flows=None, slot=0, rng=None):
         """One sampling loop as a generator that yields after enqueueing each step's (asynchronous) GPU work,
-        so several independent clips can be interleaved from one host thread (``run_concurrent``)."""
+        so several independent clips can be interleaved from one host thread (``run_concurrent``).
+        ``rng`` = (seed, unit, window) or None: where a stochastic scheduler's variance noise comes from (``_finish_step``)."""
         lat, cond, runner = self._prep(latent, text_cond, text_uncond, img_cond, slot)
         dev = lat.device
         F, _, h, w = lat.shape
@@ -301,26 +310,37 @@ class InferenceIP2PVideo(Inference):
             t = int(t)
             ops.build_unet_input(lat, cond, runner.x_in, runner.t, t, 3)
             eps = runner.run()
-            lat, pred = self._finish_step(i, t, eps, lat, text_cfg, img_cfg, guidance_rescale, stats, ref, noise_correct_step, flows)
+            lat, pred = self._finish_step(i, t, eps, lat, text_cfg, img_cfg, guidance_rescale, stats, ref, noise_correct_step, flows, rng=rng)
             all_latent.append(lat[None])
             all_pred.append(pred[None])
             yield i
         return {"latent": lat[None], "all_latent": all_latent, "all_pred": all_pred}
 
-    def _finish_step(self, i, t, eps, lat, text_cfg, img_cfg, guidance_rescale, stats, ref, noise_correct_step, flows, noise=None, bstride=0):
+    def _finish_step(self, i, t, eps, lat, text_cfg, img_cfg, guidance_rescale, stats, ref, noise_correct_step, flows, noise=None, bstride=0,
+                     rng=None):
         """Everything of one sampling step behind the UNet for ONE clip: CFG combine (+ rescale), noise correction, scheduler
         step (inference.py:197-213, 270-277, 367-386).  eps: the clip's three branch predictions [3*F*h*w, 4] fp32, or (bstride > 0,
-        the branch-major stack) a view that starts at its first branch with bstride fp32 elements between the branches."""
+        the branch-major stack) a view that starts at its first branch with bstride fp32 elements between the branches.
+        Variance noise of a stochastic scheduler, in order of precedence: an injected tensor (``noise`` / ``variance_noises[i]``), the
+        seeded stream of ``rng`` = (seed, unit, window) - generated inside the step kernel, no tensor -, a ``torch.randn`` draw."""
         dev = lat.device
         F, _, h, w = lat.shape
         if stats is not None:
             ops.cfg_stats(eps, stats, F, h, w, text_cfg, img_cfg, branch_stride=bstride)
         co = self.scheduler.coefficients(t)
+        seeded = {}
         if self.scheduler.stochastic and co["coef"][3] != 0.0:
             if noise is None:
                 inj = self.variance_noises[i] if self.variance_noises is not None else None
-                noise = (inj[0].to(device=dev, dtype=torch.float32).contiguous() if inj is not None
-                         else torch.randn(lat.shape, device=dev, dtype=torch.float32))
+                if inj is not None:
+                    noise = inj[0].to(device=dev, dtype=torch.float32).contiguous()
+                elif rng is not None:
+                    # This runs OUTSIDE the captured UNet graph, so the step index is a host integer packed into the stream id.  Should
+                    # the step kernel ever move inside a capture, the index has to come from device memory: a captured launch replays
+                    # the arguments it was captured with.
+                    seeded = dict(noise_seed=rng[0], noise_stream=stream_id(STEP, rng[1], rng[2], i))
+                else:
+                    noise = torch.randn(lat.shape, device=dev, dtype=torch.float32)
         else:
             noise = None
         new_lat, pred = torch.empty_like(lat), torch.empty_like(lat)
@@ -333,10 +353,10 @@ class InferenceIP2PVideo(Inference):
             ops.cfg_step(eps, lat, nbranch=3, eps_out=eps_cfg, **common)
             dq = ops.flow_correction(eps_cfg, lat, ref, flows, co["sqrt_a"], co["sqrt_1ma"])
             ops.cfg_step(eps_cfg, lat, nbranch=0, coef=co["coef"], latent_out=new_lat, pred_x0=pred, latent_ref=ref,
-                         correct=2, delta_q=dq, noise=noise, sqrt_a=co["sqrt_a"], sqrt_1ma=co["sqrt_1ma"])
+                         correct=2, delta_q=dq, noise=noise, sqrt_a=co["sqrt_a"], sqrt_1ma=co["sqrt_1ma"], **seeded)
         else:
             ops.cfg_step(eps, lat, nbranch=3, coef=co["coef"], latent_out=new_lat, pred_x0=pred,
-                         latent_ref=ref if correct else None, correct=1 if correct else 0, noise=noise, **common)
+                         latent_ref=ref if correct else None, correct=1 if correct else 0, noise=noise, **seeded, **common)
         return new_lat, pred
 
     @torch.no_grad()
@@ -345,7 +365,8 @@ class InferenceIP2PVideo(Inference):
         ``run_concurrent``) as ONE batch: the 3 CFG branches of all n clips are stacked into every UNet launch
         (B = 3n; statistics stay per sample), so weights are read once per group of clips, every launch fills the chip
         and the lowest UNet levels need no split-K.  All clips must share shapes, ``start_time`` and the scheduler;
-        guidance scales may differ.  Also the path of a batched ``__call__`` (inference.py:183-187 works for any b).
+        guidance scales may differ.  A call's ``seed`` / ``unit`` / ``window`` select its seeded noise streams as in ``__call__``: a unit's
+        result then does not depend on what it is stacked with.  Also the path of a batched ``__call__`` (inference.py:183-187 works for any b).
         (Round 4 measured two stacks of 5 clips running concurrently on two HIP streams against one stack of 10: 14.02 vs 14.50 frames/s -
         the persistent kernels own every CU, a second chain only fills tails and pays for it with half-sized launches.)"""
         n = len(calls)
@@ -401,7 +422,7 @@ class InferenceIP2PVideo(Inference):
                               ncs=kw.get("noise_correct_step", 1.0) if ref is not None else 0.0,
                               text_cfg=kw.get("text_cfg", 7.5), img_cfg=kw.get("img_cfg", 1.2), gr=gr,
                               stats=torch.empty(2, device=dev, dtype=torch.float32) if gr > 0 else None,
-                              noises=kw.get("noises"), all_latent=[], all_pred=[]))
+                              noises=kw.get("noises"), rng=_rng_of(kw), all_latent=[], all_pred=[]))
         F, _, h, w = clips[0]["lat"].shape
         # BRANCH-major stack: sample br * n + c = branch br of clip c - the branches (no text, video) and (text, video), whose UNet inputs
         # are identical (inference.py:183-194), are the contiguous samples [n, 3n): the UNet computes their common prefix once (cfg_clips)
@@ -417,7 +438,8 @@ class InferenceIP2PVideo(Inference):
             for c, cl in enumerate(clips):
                 noise = cl["noises"][i] if cl["noises"] is not None else None
                 cl["lat"], pred = self._finish_step(i, t, eps[c * rows1:], cl["lat"], cl["text_cfg"], cl["img_cfg"], cl["gr"],
-                                                    cl["stats"], cl["ref"], cl["ncs"], cl["flows"], noise=noise, bstride=n * rows1 * 4)
+                                                    cl["stats"], cl["ref"], cl["ncs"], cl["flows"], noise=noise, bstride=n * rows1 * 4,
+                                                    rng=cl["rng"])
                 cl["all_latent"].append(cl["lat"][None])
                 cl["all_pred"].append(pred[None])
             yield
@@ -425,10 +447,14 @@ class InferenceIP2PVideo(Inference):
 
     def _batched_call(self, latent, text_cond, text_uncond, img_cond, latent_ref=None, **kw):
         """b > 1: the reference stacks the batch into the UNet call (inference.py:183-194); here every batch entry is a clip of
-        ``run_stacked``.  A stochastic scheduler draws ONE [b,F,4,h,w] normal per step like the reference and slices it."""
+        ``run_stacked``.  A stochastic scheduler draws ONE [b,F,4,h,w] normal per step like the reference and slices it - or, with
+        ``seed``, batch entry j takes the streams of unit ``unit`` + j."""
         b = latent.shape[0]
         noises = None
-        if self.scheduler.stochastic and self.variance_noises is None:
+        seed, unit = kw.pop("seed", None), kw.pop("unit", 0)
+        if seed is not None:
+            kw["seed"] = seed
+        if self.scheduler.stochastic and self.variance_noises is None and seed is None:
             dev = self.unet.device
             steps = len(self.scheduler.timesteps[kw.get("start_time", 0):])
             draws = [torch.randn(latent.shape, device=dev, dtype=torch.float32) for _ in range(steps)]
@@ -446,6 +472,8 @@ class InferenceIP2PVideo(Inference):
                     c[k] = kw[k][j:j + 1]
             if noises is not None:
                 c["noises"] = noises[j]
+            if seed is not None:
+                c["unit"] = unit + j
             calls.append(c)
         res = self.run_stacked(calls)
         steps = len(res[0]["all_latent"])
@@ -469,7 +497,7 @@ class InferenceIP2PVideo(Inference):
             st.wait_stream(main)
             args = dict(latent=kw["latent"], text_cond=kw["text_cond"], text_uncond=kw["text_uncond"], img_cond=kw["img_cond"],
                         text_cfg=kw.get("text_cfg", 7.5), img_cfg=kw.get("img_cfg", 1.2), start_time=kw.get("start_time", 0),
-                        guidance_rescale=kw.get("guidance_rescale", 0.0), slot=slot)
+                        guidance_rescale=kw.get("guidance_rescale", 0.0), slot=slot, rng=_rng_of(kw))
             if kw.get("latent_ref") is not None:
                 args.update(latent_ref=kw["latent_ref"], noise_correct_step=kw.get("noise_correct_step", 1.0))
             gens.append((st, self._loop_gen(**args)))
@@ -491,20 +519,25 @@ class InferenceIP2PVideo(Inference):
     # ---- reference call surface ----------------------------------------------------------------------
     @torch.no_grad()
     def __call__(self, latent, text_cond, text_uncond, img_cond, text_cfg=7.5, img_cfg=1.2, start_time=0,
-                 guidance_rescale=0.0):
+                 guidance_rescale=0.0, seed=None, unit=0, window=0):
+        """``seed`` (default None: the draws of ``torch.randn``, as before): a stochastic scheduler's variance noise of step i comes from
+        the seeded stream ``rng.stream_id(STEP, unit, window, i)`` - a pure function of (seed, unit, window, step, element), whatever
+        else runs.  Injected ``variance_noises`` win over it; a deterministic scheduler ignores it."""
         if latent.shape[0] != 1:
             return self._batched_call(latent, text_cond, text_uncond, img_cond, text_cfg=text_cfg, img_cfg=img_cfg, start_time=start_time,
-                                      guidance_rescale=guidance_rescale)
-        return self._loop(latent, text_cond, text_uncond, img_cond, text_cfg, img_cfg, start_time, guidance_rescale)
+                                      guidance_rescale=guidance_rescale, seed=seed, unit=unit, window=window)
+        return self._loop(latent, text_cond, text_uncond, img_cond, text_cfg, img_cfg, start_time, guidance_rescale,
+                          rng=_rng_of(dict(seed=seed, unit=unit, window=window)))
 
     @torch.no_grad()
     def second_clip_forward(self, latent, text_cond, text_uncond, img_cond, latent_ref, noise_correct_step=1.0,
-                            text_cfg=7.5, img_cfg=1.2, start_time=0, guidance_rescale=0.0):
+                            text_cfg=7.5, img_cfg=1.2, start_time=0, guidance_rescale=0.0, seed=None, unit=0, window=0):
         if latent.shape[0] != 1:
             return self._batched_call(latent, text_cond, text_uncond, img_cond, latent_ref=latent_ref, noise_correct_step=noise_correct_step,
-                                      text_cfg=text_cfg, img_cfg=img_cfg, start_time=start_time, guidance_rescale=guidance_rescale)
+                                      text_cfg=text_cfg, img_cfg=img_cfg, start_time=start_time, guidance_rescale=guidance_rescale,
+                                      seed=seed, unit=unit, window=window)
         return self._loop(latent, text_cond, text_uncond, img_cond, text_cfg, img_cfg, start_time, guidance_rescale,
-                          latent_ref=latent_ref, noise_correct_step=noise_correct_step)
+                          latent_ref=latent_ref, noise_correct_step=noise_correct_step, rng=_rng_of(dict(seed=seed, unit=unit, window=window)))
 
 
 class InferenceIP2PVideoOpticalFlow(InferenceIP2PVideo):
@@ -545,11 +578,12 @@ class InferenceIP2PVideoOpticalFlow(InferenceIP2PVideo):
     @torch.no_grad()
     def second_clip_forward(self, latent, text_cond, text_uncond, img_cond, latent_ref, ref_images=None,
                             query_images=None, noise_correct_step=1.0, text_cfg=7.5, img_cfg=1.2, start_time=0,
-                            guidance_rescale=0.0, flows=None):
+                            guidance_rescale=0.0, flows=None, seed=None, unit=0, window=0):
         if flows is None:
             assert ref_images.shape[0] == 1, "only support batch size 1"
             flows = self.obtain_flow_batched(ref_images[0], query_images[0])
         h, w = latent.shape[-2:]
         small = self._latent_flows(flows, latent.shape[1] - latent_ref.shape[1], h, w)
         return self._loop(latent, text_cond, text_uncond, img_cond, text_cfg, img_cfg, start_time, guidance_rescale,
-                          latent_ref=latent_ref, noise_correct_step=noise_correct_step, flows=small)
+                          latent_ref=latent_ref, noise_correct_step=noise_correct_step, flows=small,
+                          rng=_rng_of(dict(seed=seed, unit=unit, window=window)))

@@ -19,9 +19,13 @@ class InstructP2PVideoModel:
         self.unet, self.vae, self.text_model, self.scale_factor = unet, vae, text_model, scale_factor
 
     @torch.no_grad()
-    def encode_image_to_latent(self, image, noise=None):
-        """image [b,f,3,H,W] in [-1,1] -> latent [b,f,4,H/8,W/8] (posterior sample x scale_factor)."""
+    def encode_image_to_latent(self, image, noise=None, seed=None, unit=0):
+        """image [b,f,3,H,W] in [-1,1] -> latent [b,f,4,H/8,W/8] (posterior sample x scale_factor).  ``seed`` (without ``noise``, which
+        wins): batch entry j takes the ENC stream of unit ``unit`` + j over its own [f,4,h,w] (insv2v/rng.py)."""
         b, f = image.shape[:2]
+        if noise is None and seed is not None:
+            z = torch.stack([self.vae.encode(image[j], scale=self.scale_factor, seed=seed, unit=unit + j) for j in range(b)], 0)
+            return z
         z = self.vae.encode(image.reshape(b * f, *image.shape[2:]),
                             None if noise is None else noise.reshape(b * f, *noise.shape[2:]), scale=self.scale_factor)
         return z.reshape(b, f, *z.shape[1:])

@@ -9,6 +9,7 @@ import os
 import torch
 
 from . import _lib
+from .rng import as_int64
 from ._lib import GemmDesc, GroupNormDesc, LayerNormDesc, AttentionDesc, StepDesc, FfnDesc, RowLinDesc, TattnDesc, XattnDesc, WinogradInDesc, WinogradOutDesc, check
 
 ACT_NONE, ACT_SILU, ACT_GEGLU, ACT_QUICK_GELU = 0, 1, 2, 3
@@ -717,7 +718,9 @@ def build_unet_input(latent, img_cond, out, t_out, timestep, nbranch, branch_row
 
 def cfg_step(eps_in, latent, *, nbranch, text_cfg=1.0, img_cfg=1.0, sqrt_a=1.0, sqrt_1ma=0.0, coef=(0, 0, 0, 0),
              latent_out=None, pred_x0=None, eps_out=None, latent_ref=None, correct=0, delta_q=None, noise=None,
-             rescale_stats=None, guidance_rescale=0.0, branch_stride=0):
+             rescale_stats=None, guidance_rescale=0.0, branch_stride=0, noise_seed=None, noise_stream=0):
+    """``noise_seed`` / ``noise_stream``: the step's variance noise is generated inside the kernel from the seeded stream (element = flat
+    index of [F,4,h,w]) instead of read from ``noise``; passing both is rejected by the kernel."""
     lib = _lib.load()
     F, _, h, w = latent.shape[-4:]
     d = StepDesc()
@@ -729,6 +732,8 @@ def cfg_step(eps_in, latent, *, nbranch, text_cfg=1.0, img_cfg=1.0, sqrt_a=1.0, 
     d.text_cfg, d.img_cfg, d.sqrt_a, d.sqrt_1ma = text_cfg, img_cfg, sqrt_a, sqrt_1ma
     d.c_x0, d.c_eps, d.c_xt, d.c_noise = coef
     d.guidance_rescale, d.branch_stride = guidance_rescale, branch_stride
+    if noise_seed is not None:
+        d.noise_seed, d.noise_stream, d.noise_on = as_int64(noise_seed), as_int64(noise_stream, "stream"), 1
     check(lib.insv2v_cfg_step(_byref(d), _stream()), "insv2v_cfg_step")
 
 
@@ -786,13 +791,40 @@ def nhwc_to_nchw_f32(x, N, Cc, H, W, scale=1.0):
     return out
 
 
-def posterior_sample(moments, noise, N, H, W, scale):
+def posterior_sample(moments, noise, N, H, W, scale, seed=None, stream=0, offset=0):
+    """``seed`` (with ``noise=None``): the noise is generated inside the kernel, element i of the sample from element ``offset`` + i of the
+    normal stream (seed, stream)."""
     lib = _lib.load()
-    _req(moments, torch.float32, "posterior.moments"), _req(noise, torch.float32, "posterior.noise")
+    _req(moments, torch.float32, "posterior.moments")
     z = torch.empty((N, 4, H, W), device=moments.device, dtype=torch.float32)
+    if seed is not None:
+        if noise is not None:
+            raise _lib.HipKernelError("posterior_sample: pass noise or seed, not both")
+        check(lib.insv2v_posterior_sample_seeded(moments.data_ptr(), z.data_ptr(), N, H, W, moments.stride(0), scale,
+                                                 as_int64(seed), as_int64(stream, "stream"), int(offset), _stream()), "insv2v_posterior_sample_seeded")
+        return z
+    _req(noise, torch.float32, "posterior.noise")
     check(lib.insv2v_posterior_sample(moments.data_ptr(), noise.contiguous().data_ptr(), z.data_ptr(), N, H, W,
                                       moments.stride(0), scale, _stream()), "insv2v_posterior_sample")
     return z
+
+
+def randn(shape_or_out, seed, stream, offset=0, raw=False, device=None):
+    """Elements [offset, offset + n) of the seeded stream (seed, stream) (include/insv2v_hip.h, "seeded noise"): fp32 normals, or with
+    ``raw`` the 32-bit words' bit patterns as int32.  ``shape_or_out``: a shape (a new tensor on ``device`` / the current GPU is
+    returned) or a contiguous CUDA tensor to fill (float32; int32 also with ``raw``)."""
+    lib = _lib.load()
+    if torch.is_tensor(shape_or_out):
+        out = shape_or_out
+        if not (out.is_cuda and out.is_contiguous() and (out.dtype == torch.float32 or (raw and out.dtype == torch.int32))):
+            raise _lib.HipKernelError(f"randn: expected a contiguous CUDA float32 tensor, got {out.device} {out.dtype}")
+    else:
+        shape = (shape_or_out,) if isinstance(shape_or_out, int) else tuple(shape_or_out)
+        out = torch.empty(shape, device=device if device is not None else torch.device("cuda", torch.cuda.current_device()),
+                          dtype=torch.int32 if raw else torch.float32)
+    check(lib.insv2v_randn(out.data_ptr(), out.numel(), as_int64(seed), as_int64(stream, "stream"), int(offset), int(bool(raw)), _stream()),
+          "insv2v_randn")
+    return out
 
 
 # ----------------------------------------------------------------------------- optical-flow estimator (insv2v/raft.py)

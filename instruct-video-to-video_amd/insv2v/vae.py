@@ -10,6 +10,7 @@ O = P v, with v^T produced directly by a GEMM so no transpose kernel is needed.
 import torch
 
 from . import ops
+from .rng import stream_id, ENC
 from .unet import prep_conv3x3, prep_linear, prep_norm, _dev
 
 EPS = 1e-6
@@ -150,10 +151,15 @@ class AutoencoderKL:
         return ops.gemm(t, *self.quant, out_fp32=True), geom
 
     @torch.no_grad()
-    def encode(self, x, noise=None, scale=1.0):
+    def encode(self, x, noise=None, scale=1.0, seed=None, unit=0, offset=0):
         """Posterior SAMPLE (autoencoder.py:89-95); ``noise`` [N,4,h,w] defaults to a CPU randn like the
-        reference (autoencoder.py:22).  Returns fp32 [N,4,h,w] times ``scale``."""
+        reference (autoencoder.py:22).  Returns fp32 [N,4,h,w] times ``scale``.
+        ``seed`` (without ``noise``, which wins): the noise is generated inside the sampling kernel from the unit's ENC stream
+        (insv2v/rng.py), element = ``offset`` + flat index of [N,4,h,w]; a video encoded in several calls passes each call's first
+        frame times 4*h*w as ``offset`` and gets the sample of one call."""
         mom, (N, h, w) = self.moments(x)
+        if noise is None and seed is not None:
+            return ops.posterior_sample(mom, None, N, h, w, scale, seed=seed, stream=stream_id(ENC, unit), offset=offset)
         if noise is None:
             noise = torch.randn((N, self.embed_dim, h, w))
         noise = noise.to(device=self.device, dtype=torch.float32)
