@@ -156,7 +156,18 @@ int insv2v_gemm(const insv2v_gemm_desc* d, insv2v_stream_t stream);
  * GroupNorm samples (gn_images_per_sample); partial row statistics (stats_parts > 0) are finalised over the whole problem first.  Such a
  * problem cannot emit stats_out (INSV2V_EUNSUPPORTED, like every problem that cannot), is not batched and takes no forced split-K.
  * insv2v_set_operand_window(bytes) replaces the window size (0 = default: 2 GiB less 1 MiB) and returns the previous value; it exists so
- * that tests can drive small problems through the split path - the product never calls it. */
+ * that tests can drive small problems through the split path - the product never calls it.
+ * The same holds for the fused row kernels, and they obey the same hook: insv2v_ffn_fused, insv2v_tattn_fused / _attn and
+ * insv2v_xattn_fused / _attn take x, out, post_residual and pre_residual of any size; a problem beyond one window (2^31 bytes, or the
+ * hook's) runs as ranges of whole units, one launch each, bit-identical to one launch.  What has to fit one window is ONE unit of the
+ * widest operand (INSV2V_EUNSUPPORTED otherwise, before anything is launched):
+ *   insv2v_ffn_fused                      a 128-row tile
+ *   insv2v_tattn_fused, insv2v_tattn_attn one sample: frames x HW rows
+ *   insv2v_xattn_fused, insv2v_xattn_attn one sample: rows_per_sample rows; and the K / V streams of ALL samples (samples x 176 KiB
+ *                                         at C = 320, x 320 KiB at C = 640)
+ * insv2v_rowlin (a 256-row tile, or a wave's 32 rows with gn_ab) and insv2v_attention base their descriptors inside the kernel and
+ * do not look at the hook.  The Python host restates this arithmetic (insv2v/fused.py check_operand_windows) and refuses a geometry
+ * that cannot run before the first launch of a forward. */
 int64_t insv2v_set_operand_window(int64_t bytes);
 /* Number of column tiles (= partial statistics per row) insv2v_gemm will write for this problem when stats_out is set;
  * 0 if the problem cannot emit statistics (the caller then uses insv2v_layernorm_stats on the output). */

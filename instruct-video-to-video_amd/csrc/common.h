@@ -99,6 +99,8 @@ static inline hipStream_t as_stream(insv2v_stream_t s) { return (hipStream_t)s; 
 // call with compare-exchange - instead of one unsynchronised static per translation unit.)
 bool insv2v_one_device_check();
 static inline bool one_device() { return insv2v_one_device_check(); }
+// The window set by insv2v_set_operand_window (gemm.hip), 0 if none: the launchers that split a problem into in-window ranges obey it.
+int64_t insv2v_operand_window_override();
 static inline int launch_status() {
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : (int)e;

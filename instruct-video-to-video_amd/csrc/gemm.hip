@@ -1124,6 +1124,7 @@ extern "C" int64_t insv2v_set_operand_window(int64_t bytes) {
     return prev;
 }
 static int64_t operand_window() { return g_operand_window > 0 ? g_operand_window : ((int64_t)1 << 31) - ((int64_t)1 << 20); }
+int64_t insv2v_operand_window_override() { return g_operand_window; }   // (the row launchers split by the same hook: rows_common.h)
 // Does an operand of this problem reach beyond one window (insv2v_gemm then runs it as row / image ranges, without output statistics)?
 // One helper for insv2v_gemm and insv2v_gemm_stats_parts, so that the two cannot disagree.
 static bool beyond_window(const insv2v_gemm_desc& d) {

@@ -279,6 +279,29 @@ int num_cus() {
     return n;
 }
 
+// Operands beyond one 2 GiB descriptor.  The fused kernels address x / out / residual through descriptors built at the operand's base, with
+// 32-bit lane offsets.  Their launchers run a problem whose operands reach beyond the window as RANGES OF WHOLE UNITS - 128-row tiles
+// (feed-forward), samples (temporal and text attention: a wave / a tile never reads across a sample) - one launch per range with the base
+// pointers advanced on the host, as insv2v_gemm does for row / image ranges.  The kernels do not know: an in-window problem is one launch,
+// exactly as before, and a row's arithmetic does not depend on the range it falls in.  unit_bytes = the widest operand's bytes per unit;
+// a unit that does not fit by itself is refused; whole_bytes = the widest operand's extent where the last unit is partial.  launch(u0, nu)
+// launches units [u0, u0 + nu).  The window is the hardware's 2^31 bytes unless a test shrank it (insv2v_set_operand_window), so that
+// small problems can take this path.
+template <class Fn>
+int launch_unit_ranges(int64_t units, int64_t unit_bytes, Fn&& launch, int64_t whole_bytes = -1) {
+    const int64_t ov = insv2v_operand_window_override(), lim = ov > 0 ? ov : (int64_t)1 << 31;
+    if (units <= 0 || unit_bytes <= 0 || unit_bytes >= lim) return INSV2V_EUNSUPPORTED;
+    if ((whole_bytes >= 0 ? whole_bytes : units * unit_bytes) < lim) return launch((int64_t)0, units);
+    int64_t per = (lim - 1) / unit_bytes;
+    const int64_t nparts = (units + per - 1) / per;
+    per = (units + nparts - 1) / nparts;   // parts as even as possible
+    for (int64_t u0 = 0; u0 < units; u0 += per) {
+        const int rc = launch(u0, units - u0 < per ? units - u0 : per);
+        if (rc != 0) return rc;
+    }
+    return 0;
+}
+
 template <class Args>
 int launch_rows(const void* kernel, bool& attr_set, int lds, const Args& args, int M, hipStream_t s, int wgs_per_cu = 1) {
     if (!attr_set) {

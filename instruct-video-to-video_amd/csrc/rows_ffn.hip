@@ -1,5 +1,6 @@
 // Fused feed-forward (insv2v_ffn_fused) and the K = 320 / 640 row Linear (insv2v_rowlin); the register-resident scheme: rows_common.h
 #include "rows_common.h"
+#include <algorithm>
 #include <cstdlib>
 
 namespace {
@@ -486,15 +487,20 @@ extern "C" int insv2v_ffn_fused(const insv2v_ffn_desc* dp, insv2v_stream_t strea
     if (!d.x || !d.out || !d.wstream || d.M <= 0) return INSV2V_EINVAL;
     if (d.C != FC || d.hidden != 4 * FC) return INSV2V_EUNSUPPORTED;
     if ((d.ldx & 7) || (d.ldo & 7) || ((uintptr_t)d.x & 15) || ((uintptr_t)d.out & 15) || ((uintptr_t)d.wstream & 15)) return INSV2V_EINVAL;
-    if ((int64_t)d.M * d.ldx * 2 >= ((int64_t)1 << 31) || (int64_t)d.M * d.ldo * 2 >= ((int64_t)1 << 31)) return INSV2V_EUNSUPPORTED;
+    if (d.post && (!d.post_residual || (d.ld_post & 7) || ((uintptr_t)d.post_residual & 15))) return INSV2V_EINVAL;
     const FfnArgs a = {(const half_t*)d.x, (half_t*)d.out, (const half_t*)d.wstream, (const half_t*)d.post_residual, d.ldx, d.ldo, d.ld_post, d.M, d.eps};
-    if (d.post) {
-        if (!d.post_residual || (d.ld_post & 7) || ((uintptr_t)d.post_residual & 15) || (int64_t)d.M * d.ld_post * 2 >= ((int64_t)1 << 31)) return INSV2V_EINVAL;
-        static bool post_attr = false;
-        return launch_rows((const void*)ffn_fused_kernel<true>, post_attr, FFN_NS * FFN_SLOT_FR * 1024, a, d.M, as_stream(stream));
-    }
-    static bool attr_set = false;
-    return launch_rows((const void*)ffn_fused_kernel<false>, attr_set, FFN_NS * FFN_SLOT_FR * 1024, a, d.M, as_stream(stream));
+    // x, out and post_residual may each exceed the 2 GiB window: ranges of whole 128-row tiles, one launch each (launch_unit_ranges)
+    const int64_t ld = std::max(std::max(d.ldx, d.ldo), d.post ? d.ld_post : (int64_t)0);
+    return launch_unit_ranges(((int64_t)d.M + 127) / 128, 128 * ld * 2, [&](int64_t t0, int64_t nt) {
+        FfnArgs r = a;
+        const int64_t m0 = t0 * 128;
+        r.x += m0 * a.ldx; r.out += m0 * a.ldo;
+        if (d.post) r.res2 += m0 * a.ldr2;
+        r.M = (int)std::min(nt * 128, (int64_t)d.M - m0);
+        static bool post_attr = false, attr_set = false;
+        if (d.post) return launch_rows((const void*)ffn_fused_kernel<true>, post_attr, FFN_NS * FFN_SLOT_FR * 1024, r, r.M, as_stream(stream));
+        return launch_rows((const void*)ffn_fused_kernel<false>, attr_set, FFN_NS * FFN_SLOT_FR * 1024, r, r.M, as_stream(stream));
+    }, (int64_t)d.M * ld * 2);
 }
 
 // Size in fp16 elements of the weight stream insv2v_ffn_fused expects for (C, hidden); 0 if unsupported.

@@ -1,5 +1,6 @@
 // Fused temporal attention: insv2v_tattn_fused (C = 320) and insv2v_tattn_attn (C = 640); the register-resident scheme: rows_common.h
 #include "rows_common.h"
+#include <algorithm>
 
 namespace {
 // ===================================================================================================== temporal attention block
@@ -300,16 +301,21 @@ static int launch_tattn(const insv2v_tattn_desc* dp, int C, const void* const (&
     if (!d.x || !d.out || !d.wstream || d.samples <= 0 || d.HW <= 0) return INSV2V_EINVAL;
     if (d.C != C || d.heads != TA_H || d.frames < 1 || d.frames > 32) return INSV2V_EUNSUPPORTED;
     if ((d.ldx & 7) || (d.ldo & 7) || ((uintptr_t)d.x & 15) || ((uintptr_t)d.out & 15) || ((uintptr_t)d.wstream & 15)) return INSV2V_EINVAL;
-    const int64_t rows = (int64_t)d.samples * d.frames * d.HW;
-    if (rows * d.ldx * 2 >= ((int64_t)1 << 31) || rows * d.ldo * 2 >= ((int64_t)1 << 31)) return INSV2V_EUNSUPPORTED;
-    TattnWinArgs a;
-    static_cast<TattnArgs&>(a) = {(const half_t*)d.x, (half_t*)d.out, (const half_t*)d.wstream, d.ldx, d.ldo, d.HW, d.samples * d.HW, d.eps, d.scale};
-    a.frames = d.frames;
     const int v = d.frames == TA_F ? 0 : d.frames < TA_F ? 1 : 2, FP = v == 2 ? 32 : 16;
-    // launch_rows sizes the grid from a row count in 128-row tiles: a tile here is 8 pixels x 16 frame slots or 4 pixels x 32 = 128 rows
-    const int M = (int)((int64_t)a.npix * FP > 0x7fffffff ? 0x7fffffff : a.npix * FP);
-    if (v == 0) return launch_rows(kernels[0], attr_set[0], 9 * 16 * 1024, static_cast<const TattnArgs&>(a), M, as_stream(stream));
-    return launch_rows(kernels[v], attr_set[v], 9 * 16 * 1024, a, M, as_stream(stream));
+    // x and out may each exceed the 2 GiB window: ranges of whole samples, one launch each (launch_unit_ranges; a wave never reads across
+    // a sample, so one sample's frames x HW rows are what has to fit)
+    const int64_t srows = (int64_t)d.frames * d.HW;
+    return launch_unit_ranges(d.samples, srows * std::max(d.ldx, d.ldo) * 2, [&](int64_t s0, int64_t ns) {
+        if (ns * d.HW * FP > 0x7fffffff) return (int)INSV2V_EUNSUPPORTED;
+        TattnWinArgs a;
+        static_cast<TattnArgs&>(a) = {(const half_t*)d.x + s0 * srows * d.ldx, (half_t*)d.out + s0 * srows * d.ldo, (const half_t*)d.wstream,
+                                      d.ldx, d.ldo, d.HW, (int)(ns * d.HW), d.eps, d.scale};
+        a.frames = d.frames;
+        // launch_rows sizes the grid from a row count in 128-row tiles: a tile here is 8 pixels x 16 frame slots or 4 pixels x 32 = 128 rows
+        const int M = a.npix * FP;
+        if (v == 0) return launch_rows(kernels[0], attr_set[0], 9 * 16 * 1024, static_cast<const TattnArgs&>(a), M, as_stream(stream));
+        return launch_rows(kernels[v], attr_set[v], 9 * 16 * 1024, a, M, as_stream(stream));
+    });
 }
 
 extern "C" int insv2v_tattn_fused(const insv2v_tattn_desc* dp, insv2v_stream_t stream) {

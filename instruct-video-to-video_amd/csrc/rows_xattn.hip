@@ -1,5 +1,6 @@
 // Fused text cross-attention: insv2v_xattn_fused (C = 320) and insv2v_xattn_attn (C = 640); the register-resident scheme: rows_common.h
 #include "rows_common.h"
+#include <algorithm>
 
 namespace {
 // ===================================================================================================== cross-attention block
@@ -309,6 +310,8 @@ __global__ __launch_bounds__(256, 1) void xattn_fused_kernel(XattnArgs p) {
 }  // namespace
 
 // Both launchers: validation and the argument block; kv_fr = fragments of one sample's K / V stream
+// (x, out and pre_residual may each exceed the 2 GiB window: launch_xattn runs ranges of whole samples; the K / V streams of all samples
+// stay inside one window)
 static int xattn_args(const insv2v_xattn_desc* dp, int C, int kv_fr, XattnArgs& a) {
     if (!one_device()) return INSV2V_EINVAL;
     if (!dp) return INSV2V_EINVAL;
@@ -318,12 +321,27 @@ static int xattn_args(const insv2v_xattn_desc* dp, int C, int kv_fr, XattnArgs& 
     if (d.M % d.rows_per_sample) return INSV2V_EUNSUPPORTED;   // whole samples: each gets its own 128-row tiles (XattnTile)
     if ((d.ldx & 7) || (d.ldo & 7) || ((uintptr_t)d.x & 15) || ((uintptr_t)d.out & 15) || ((uintptr_t)d.wstream & 15) || ((uintptr_t)d.kvstream & 15)) return INSV2V_EINVAL;
     const int64_t lim = (int64_t)1 << 31;
-    if ((int64_t)d.M * d.ldx * 2 >= lim || (int64_t)d.M * d.ldo * 2 >= lim || (int64_t)(d.M / d.rows_per_sample) * kv_fr * 1024 >= lim) return INSV2V_EUNSUPPORTED;
+    if ((int64_t)(d.M / d.rows_per_sample) * kv_fr * 1024 >= lim) return INSV2V_EUNSUPPORTED;
     a = {(const half_t*)d.x, (half_t*)d.out, (const half_t*)d.wstream, (const half_t*)d.kvstream, d.ldx, d.ldo, d.M, d.rows_per_sample,
          d.ctx_len, d.eps, d.scale, nullptr, 0, 0, 0};
     a.tiles_per_sample = (d.rows_per_sample + 127) / 128;
-    a.ntiles = (d.M / d.rows_per_sample) * a.tiles_per_sample;
+    a.ntiles = 0;   // (per range: launch_xattn)
     return 0;
+}
+// ranges of whole samples, one launch each (launch_unit_ranges): the row operands and the samples' K / V streams advance together
+static int launch_xattn(const void* kernel, bool& attr_set, const XattnArgs& a, int kv_fr, insv2v_stream_t stream) {
+    const int64_t ld = std::max(std::max(a.ldx, a.ldo), a.pre_res ? a.ld_pre : (int64_t)0);
+    return launch_unit_ranges(a.M / a.rows_per_sample, (int64_t)a.rows_per_sample * ld * 2, [&](int64_t s0, int64_t ns) {
+        if (ns * a.tiles_per_sample * 128 > 0x7fffffff) return (int)INSV2V_EUNSUPPORTED;
+        XattnArgs r = a;
+        const int64_t m0 = s0 * a.rows_per_sample;
+        r.x += m0 * a.ldx; r.out += m0 * a.ldo;
+        if (a.pre_res) r.pre_res += m0 * a.ld_pre;
+        r.kvstream += s0 * kv_fr * 512;
+        r.M = (int)(ns * a.rows_per_sample);
+        r.ntiles = (int)(ns * a.tiles_per_sample);
+        return launch_rows(kernel, attr_set, KvRing::NS * KvRing::SLOT_B, r, r.ntiles * 128, as_stream(stream));
+    });
 }
 
 extern "C" int insv2v_xattn_fused(const insv2v_xattn_desc* dp, insv2v_stream_t stream) {
@@ -332,13 +350,13 @@ extern "C" int insv2v_xattn_fused(const insv2v_xattn_desc* dp, insv2v_stream_t s
     const insv2v_xattn_desc& d = *dp;
     static bool attr_set = false;
     if (d.pre_residual) {
-        if ((d.ld_pre & 7) || ((uintptr_t)d.pre_residual & 15) || (int64_t)d.M * d.ld_pre * 2 >= ((int64_t)1 << 31)) return INSV2V_EINVAL;
+        if ((d.ld_pre & 7) || ((uintptr_t)d.pre_residual & 15)) return INSV2V_EINVAL;
         a.pre_res = (const half_t*)d.pre_residual;
         a.ld_pre = d.ld_pre;
         static bool pre_attr = false;
-        return launch_rows((const void*)xattn_fused_kernel<true>, pre_attr, KvRing::NS * KvRing::SLOT_B, a, a.ntiles * 128, as_stream(stream));
+        return launch_xattn((const void*)xattn_fused_kernel<true>, pre_attr, a, XA_KV_FR, stream);
     }
-    return launch_rows((const void*)xattn_fused_kernel<false>, attr_set, KvRing::NS * KvRing::SLOT_B, a, a.ntiles * 128, as_stream(stream));
+    return launch_xattn((const void*)xattn_fused_kernel<false>, attr_set, a, XA_KV_FR, stream);
 }
 
 // fp16 elements of the shared weight stream (q + output projections) and of ONE sample's K / V stream; 0 if unsupported
@@ -485,7 +503,7 @@ extern "C" int insv2v_xattn_attn(const insv2v_xattn_desc* dp, insv2v_stream_t st
     XattnArgs a;
     if (const int st = xattn_args(dp, 640, 4 * XB_KV_FR, a)) return st;
     static bool attr_set = false;
-    return launch_rows((const void*)xattn640_kernel, attr_set, KvRing::NS * KvRing::SLOT_B, a, a.ntiles * 128, as_stream(stream));
+    return launch_xattn((const void*)xattn640_kernel, attr_set, a, 4 * XB_KV_FR, stream);
 }
 
 // fp16 elements of the q weight stream / of ONE sample's K / V stream of insv2v_xattn_attn; 0 if unsupported

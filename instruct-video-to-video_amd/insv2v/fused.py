@@ -391,3 +391,48 @@ def unit_rows(q, seg_rows, unit):
     ups = -(-seg_rows // unit)
     s, u = divmod(q, ups)
     return s, s * seg_rows + u * unit, min(unit, seg_rows - u * unit)
+
+
+# ---- the operand window of the row kernels ------------------------------------------------------------------------------------------------
+# A kernel addresses an operand through a buffer descriptor of 2 GiB.  insv2v_rowlin bases its descriptors per row tile; the launchers of
+# the fused kernels run a problem whose operands reach beyond one window as ranges of whole units, one launch each (csrc/rows_common.h
+# launch_unit_ranges): 128-row tiles for the feed-forward, samples for the temporal and text attention.  So an operand may be of any
+# size, and what has to fit one window is ONE unit.  The arithmetic below is the launchers', restated so that a forward that cannot run
+# is refused before its first launch (DESIGN.md section 12).
+OPERAND_WINDOW = 2 ** 31
+XATTN_KV_BYTES = {320: 176 * 1024, 640: 4 * 80 * 1024}   # one sample's K / V fragment stream (XA_KV_FR, 4 XB_KV_FR fragments of 1 KiB)
+
+
+def row_kernel_extents(samples, frames, HW, C, ctx_len=77):
+    """[(entry point, what has to fit one window, bytes)] of the row kernels that serve a transformer level of C channels with
+    `samples` x `frames` x `HW` token rows: widths 320 and 640 have fused kernels, the others none (their GEMMs run oversize problems as
+    ranges, insv2v_attention rebases its descriptors)."""
+    if C not in (320, 640):
+        return []
+    sample = f"one sample of {frames} frames x {HW} pixels x {C} channels"
+    out = [("insv2v_rowlin", f"a 256-row tile of the fused q/k/v rows ({3 * C} channels)", 256 * 3 * C * 2)]
+    if C == 320:
+        out.append(("insv2v_ffn_fused", "a 128-row tile", 128 * C * 2))
+    if 1 <= frames <= 32:
+        out.append(("insv2v_tattn_fused" if C == 320 else "insv2v_tattn_attn", sample, frames * HW * C * 2))
+    if 64 < ctx_len <= 96:
+        xa = "insv2v_xattn_fused" if C == 320 else "insv2v_xattn_attn"
+        out.append((xa, sample, frames * HW * C * 2))
+        out.append((xa, f"the K / V streams of {samples} samples", samples * XATTN_KV_BYTES[C]))
+    return out
+
+
+def check_operand_windows(samples, frames, h, w, channels=(320, 640, 1280, 1280), ctx_len=77):
+    """Raise ValueError, naming the first operand that does not fit one 2 GiB window, if a UNet forward of `samples` samples x `frames`
+    frames of h x w latents cannot run on the row kernels; return None otherwise.  `channels`: the UNet's block_out_channels (level l works
+    on ceil(h / 2^l) x ceil(w / 2^l) pixels).  Pure arithmetic: nothing is loaded or launched."""
+    samples, frames, h, w = int(samples), int(frames), int(h), int(w)
+    if samples < 1 or frames < 1 or h < 1 or w < 1:
+        raise ValueError(f"check_operand_windows: {samples} samples x {frames} frames of {h} x {w} latents is not a geometry")
+    for level, C in enumerate(channels):
+        for entry, what, nbytes in row_kernel_extents(samples, frames, h * w, C, ctx_len):
+            if nbytes >= OPERAND_WINDOW:
+                raise ValueError(f"{samples} samples x {frames} frames of {h} x {w} latents (level {level}, {C} channels) cannot run: {entry} "
+                                 f"addresses {what} = {nbytes} bytes through one buffer descriptor, and that has to stay below "
+                                 f"{OPERAND_WINDOW} (2 GiB); use fewer frames per window or a smaller frame")
+        h, w = (h - 1) // 2 + 1, (w - 1) // 2 + 1

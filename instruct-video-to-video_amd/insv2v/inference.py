@@ -19,6 +19,7 @@ import weakref
 import torch
 
 from . import ops
+from .fused import check_operand_windows
 from .rng import stream_id, STEP
 from .schedulers import DDIMScheduler, DDPMScheduler
 from .flow_utils import resize_flow
@@ -236,15 +237,32 @@ MAX_CLIPS_IN_FLIGHT = int(os.environ.get("INSV2V_MAX_CLIPS", "20"))
 
 
 def max_clips_in_flight(frames=16, h=32, w=48):
-    """Clips that may be stacked into one launch chain: at most 20 (5 -> 10 clips gave +1.4 %, 10 -> 20 fills the last round of the
+    """Clips that are stacked into one launch chain BY DEFAULT: at most 20 (5 -> 10 clips gave +1.4 %, 10 -> 20 fills the last round of the
     level-0 tile grids - 22.5 -> 23 rounds instead of 11.25 -> 12 - and halves the launches per clip: +0.9 %, profiles/r04_clips20.txt), and few enough that every
-    [3 * clips * F * h * w, 640] fp16 tensor (the input of the level-0 convolutions, the GEGLU rows of level 1) fits ONE 2 GiB buffer
-    descriptor: the row kernels of the feed-forward / temporal / text attention blocks address whole operands through one - 20 for C2
-    (B = 60, 1.89 GB).  Wider operands ([.., 960] fused q/k/v rows, [.., 960 / 1920] concatenations) go through kernels that rebase
-    their descriptors (insv2v_rowlin, insv2v_attention) or through insv2v_gemm, which since round 5 runs any problem beyond the window
-    as row / image ranges - so clips of more than 16 frames (unfused temporal attention, q/k/v rows from insv2v_gemm) stack by the
-    same rule: 7 for C5 (round 4: 5)."""
+    [3 * clips * F * h * w, 640] fp16 tensor would fit ONE 2 GiB buffer descriptor: 20 for C2 (B = 60, 1.89 GB), 9 at 360 x 640, 7 for C5.
+    The window term is a default, not a kernel requirement: no kernel addresses a whole operand through one descriptor any more
+    (insv2v_rowlin and insv2v_attention rebase theirs; insv2v_gemm and the launchers of the fused row kernels run a problem beyond the
+    window as row / image / tile / sample ranges: DESIGN.md section 12), so ``run_stacked(calls, max_clips=N)`` may stack more.  What
+    cannot run at all is refused up front by ``fused.check_operand_windows``."""
     return max(1, min(MAX_CLIPS_IN_FLIGHT, (2 ** 31 - 2 ** 20) // (3 * frames * h * w * 640 * 2)))
+
+
+def stack_groups(n, cap):
+    """Sizes of the launch chains ``run_stacked`` runs n clips as under a cap of `cap` clips per chain: as few chains as the cap allows,
+    as even as possible (every distinct stack size captures its own graph), the larger ones first."""
+    n, cap = int(n), int(cap)
+    if cap < 1:
+        raise ValueError(f"a stack holds at least one clip, not {cap}")
+    if n <= cap:
+        return [n] if n > 0 else []
+    ng = -(-n // cap)
+    return [n // ng + (1 if g < n % ng else 0) for g in range(ng)]
+
+
+def _unet_channels(unet):
+    """block_out_channels of a UNet3DConditionModel (test doubles without a config: the full-width default)."""
+    cfg = getattr(unet, "cfg", None)
+    return tuple(cfg["ch"]) if isinstance(cfg, dict) and "ch" in cfg else (320, 640, 1280, 1280)
 
 
 def _rng_of(kw):
@@ -281,6 +299,7 @@ class InferenceIP2PVideo(Inference):
         lat, cond = self._clip_tensors(latent, img_cond)
         ctx = torch.cat([text_uncond, text_uncond, text_cond], dim=0)
         F, _, h, w = lat.shape
+        check_operand_windows(3, F, h, w, _unet_channels(self.unet), ctx.shape[1])   # a frame that cannot run is refused before the first launch
         runner = self._runner(3, F, h, w, ctx.shape[1], slot)
         runner.set_context(ctx)
         return lat, cond, runner
@@ -360,7 +379,7 @@ class InferenceIP2PVideo(Inference):
         return new_lat, pred
 
     @torch.no_grad()
-    def run_stacked(self, calls):
+    def run_stacked(self, calls, max_clips=None):
         """Run several independent ``__call__`` / ``second_clip_forward`` invocations (list of kwargs dicts as for
         ``run_concurrent``) as ONE batch: the 3 CFG branches of all n clips are stacked into every UNet launch
         (B = 3n; statistics stay per sample), so weights are read once per group of clips, every launch fills the chip
@@ -368,30 +387,34 @@ class InferenceIP2PVideo(Inference):
         guidance scales may differ.  A call's ``seed`` / ``unit`` / ``window`` select its seeded noise streams as in ``__call__``: a unit's
         result then does not depend on what it is stacked with.  Also the path of a batched ``__call__`` (inference.py:183-187 works for any b).
         (Round 4 measured two stacks of 5 clips running concurrently on two HIP streams against one stack of 10: 14.02 vs 14.50 frames/s -
-        the persistent kernels own every CU, a second chain only fills tails and pays for it with half-sized launches.)"""
+        the persistent kernels own every CU, a second chain only fills tails and pays for it with half-sized launches.)
+        ``max_clips``: clips per launch chain.  None (default): ``max_clips_in_flight`` of the clips' shape; an integer replaces that cap -
+        any stack that fits in memory runs (``stack_groups`` gives the chains; a geometry no kernel can address raises ValueError before
+        anything is launched, ``fused.check_operand_windows``)."""
         n = len(calls)
         if n == 0:
             return []
-        gen = self._stacked_gen(calls, 0)
+        gen = self._stacked_gen(calls, 0, max_clips)
         while True:
             try:
                 next(gen)
             except StopIteration as done:
                 return done.value
 
-    def _stacked_gen(self, calls, slot):
+    def _stacked_gen(self, calls, slot, max_clips=None):
         """Generator behind run_stacked: yields after every DDIM step (so several stacks can be interleaved), returns the result dicts."""
         n = len(calls)
-        # no more clips per launch chain than the kernels' 2 GiB operand window allows (ADVICE r3): larger stacks run as several,
-        # as even as possible (every distinct stack size captures its own graph)
+        # no more clips per launch chain than the cap - by default max_clips_in_flight (ADVICE r3), or the caller's max_clips: larger
+        # stacks run as several, as even as possible (stack_groups)
         Fc, hc, wc = calls[0]["latent"].shape[1], calls[0]["latent"].shape[-2], calls[0]["latent"].shape[-1]
-        cap = max_clips_in_flight(Fc, hc, wc)
-        if n > cap:
-            ng = -(-n // cap)
+        cap = max_clips_in_flight(Fc, hc, wc) if max_clips is None else int(max_clips)
+        groups = stack_groups(n, cap)
+        for m in set(groups):   # every chain's geometry is checked before the first one is launched
+            check_operand_windows(3 * m, Fc, hc, wc, _unet_channels(self.unet), calls[0]["text_cond"].shape[1])
+        if len(groups) > 1:
             out, k = [], 0
-            for g in range(ng):
-                m = n // ng + (1 if g < n % ng else 0)
-                out += yield from self._stacked_gen(calls[k:k + m], slot)
+            for m in groups:
+                out += yield from self._stacked_gen(calls[k:k + m], slot, m)
                 k += m
             return out
         dev = self.unet.device

@@ -380,8 +380,9 @@ _FUSE_CACHE = {}
 
 
 class operand_window:
-    """Context manager for tests: insv2v_gemm treats ``nbytes`` as the size of one operand window, so a small problem takes the path of
-    an operand beyond 2 GiB (row / image ranges, one launch each).  The product never uses it."""
+    """Context manager for tests: insv2v_gemm and the launchers of the fused row kernels (ffn_fused, tattn_*, xattn_*) treat ``nbytes`` as
+    the size of one operand window, so a small problem takes the path of an operand beyond 2 GiB (row / image / tile / sample ranges, one
+    launch each).  The product never uses it."""
 
     def __init__(self, nbytes):
         self.nbytes = int(nbytes)

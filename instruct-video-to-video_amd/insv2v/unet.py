@@ -18,7 +18,7 @@ import torch
 
 from . import ops
 from . import fused
-from .fused import pack_ffn_stream, pack_linear_stream, pack_tattn_stream, pack_tattn_qkv_stream
+from .fused import check_operand_windows, pack_ffn_stream, pack_linear_stream, pack_tattn_stream, pack_tattn_qkv_stream
 
 CPAD = 64  # implicit-GEMM K slices are 64 channels wide: conv inputs are zero-padded to this
 # GroupNorm+SiLU applied inside the patch-tiled conv (conv3x3(gn_ab=...)): parity-green, but measured SLOWER end to end on
@@ -687,6 +687,7 @@ class UNet3DConditionModel:
         self-attention) is computed once for the two and copied (DEDUP_CFG)."""
         c = self.cfg
         plan_sizes(H, W, len(c["ch"]))   # (refuses a degenerate latent; any other size runs: the upsamplers follow their skips' sizes)
+        check_operand_windows(B, F, H, W, c["ch"], ctx_len)   # (refuses, before the first launch, what no row kernel can address)
         emb = ops.timestep_embedding(t_dev, c["ch"][0], c["shift"])
         emb = ops.gemm(emb, *self.te1, act=ops.ACT_SILU)
         semb = ops.gemm(emb, *self.te2, act=ops.ACT_SILU)  # silu(emb): the only form the resnets consume
