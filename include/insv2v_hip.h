@@ -518,6 +518,41 @@ typedef struct insv2v_step_desc {
     int32_t noise_on;
 } insv2v_step_desc;
 int insv2v_cfg_step(const insv2v_step_desc* d, insv2v_stream_t stream);
+/*
+ * Multistep form of insv2v_cfg_step (DPM-Solver++ 2M in its data-prediction form, ODE and SDE): the same kernel body with one more
+ * term, a coefficient times the PREVIOUS step's x0 prediction:
+ *   prev = c_x0*x0 + c_eps*eps + c_xt*latent + c_hist*x0_hist + c_noise*noise
+ * Everything in front of that line - CFG combine, guidance rescale, correction modes, nbranch, branch_stride, eps_out / pred_x0, the
+ * seeded in-kernel noise - is insv2v_cfg_step's, and with x0_hist == NULL the call runs insv2v_cfg_step's own kernel (bit-identical results).  The descriptor holds
+ * the fields of insv2v_step_desc in their order, then:
+ *   x0_hist  fp32 [F,4,h,w] (reference layout) or NULL: the pred_x0 output of the previous executed step.  It is read while the
+ *            outputs are written: a range that overlaps latent_out, pred_x0 or eps_out returns INSV2V_EINVAL.
+ *   c_hist   its coefficient; c_hist != 0 with x0_hist == NULL returns INSV2V_EINVAL.
+ * An addition to ABI 14: insv2v_step_desc and insv2v_cfg_step are unchanged.
+ */
+typedef struct insv2v_mstep_desc {
+    const float* eps_in;
+    const float* latent;
+    const float* latent_ref;
+    const float* delta_q;
+    const float* noise;
+    const float* rescale_stats;
+    float* latent_out;
+    float* pred_x0;
+    float* eps_out;
+    int32_t nbranch, F, h, w, R;
+    int32_t correct;
+    float text_cfg, img_cfg;
+    float sqrt_a, sqrt_1ma;
+    float c_x0, c_eps, c_xt, c_noise;
+    float guidance_rescale;
+    int64_t branch_stride;
+    int64_t noise_seed, noise_stream;
+    int32_t noise_on;
+    const float* x0_hist;
+    float c_hist;
+} insv2v_mstep_desc;
+int insv2v_cfg_step_ms(const insv2v_mstep_desc* d, insv2v_stream_t stream);
 /* std over all elements of n1 (branch 1) and of the CFG-combined eps -> stats[0..1] (inference.py:18-19). */
 int insv2v_cfg_stats(const float* eps_in, float* stats, int32_t F, int32_t h, int32_t w, float text_cfg,
                      float img_cfg, int64_t branch_stride, insv2v_stream_t stream);

@@ -6,6 +6,8 @@
 #include "rng.h"
 #include <atomic>
 #include <cstdio>
+#include <cstring>
+#include <cstddef>
 
 __global__ void timestep_embedding_kernel(const float* t, half_t* out, int batch, int dim, float shift) {
     const int half_dim = dim / 2;
@@ -81,7 +83,9 @@ __device__ __forceinline__ float cfg_eps(const insv2v_step_desc& p, int f, int c
 }
 
 // one thread per (c,y,x); loops over frames so the mean over reference frames is thread-local.
-__global__ void cfg_step_kernel(insv2v_step_desc p, int do_step) {
+// MS: the multistep form (insv2v_cfg_step_ms) - one more term, c_hist times the previous step's x0 prediction; everything else is shared.
+template <bool MS>
+__device__ __forceinline__ void cfg_step_body(const insv2v_step_desc& p, int do_step, const float* x0_hist, float c_hist) {
     const int64_t hw = (int64_t)p.h * p.w;
     int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= 4 * hw) return;
@@ -116,6 +120,7 @@ __global__ void cfg_step_kernel(insv2v_step_desc p, int do_step) {
         if (do_step) {
             float x0 = (xt - p.sqrt_1ma * e) / p.sqrt_a;
             float prev = p.c_x0 * x0 + p.c_eps * e + p.c_xt * xt;
+            if (MS) prev += c_hist * x0_hist[li];
             // seeded (ABI 14): the variance noise is element li of (noise_seed, noise_stream), generated here - no tensor of it exists
             if (p.noise) prev += p.c_noise * p.noise[li];
             else if (p.noise_on) prev += p.c_noise * rng_normal_at(p.noise_seed, p.noise_stream, li);
@@ -124,20 +129,53 @@ __global__ void cfg_step_kernel(insv2v_step_desc p, int do_step) {
         }
     }
 }
-extern "C" int insv2v_cfg_step(const insv2v_step_desc* dp, insv2v_stream_t stream) {
-    if (!dp) return INSV2V_EINVAL;
-    insv2v_step_desc d = *dp;
+__global__ void cfg_step_kernel(insv2v_step_desc p, int do_step) { cfg_step_body<false>(p, do_step, nullptr, 0.f); }
+__global__ void cfg_step_ms_kernel(insv2v_step_desc p, int do_step, const float* x0_hist, float c_hist) {
+    cfg_step_body<true>(p, do_step, x0_hist, c_hist);
+}
+// argument checks shared by both entry points; normalises d in place
+static int cfg_step_check(insv2v_step_desc& d) {
     if (!d.eps_in || !d.latent) return INSV2V_EINVAL;
     if (d.nbranch != 0 && d.nbranch != 1 && d.nbranch != 3) return INSV2V_EINVAL;
     if (d.correct < 0 || d.correct > 2 || d.branch_stride < 0) return INSV2V_EINVAL;
     if (d.correct && (!d.latent_ref || d.R <= 0 || d.R > d.F)) return INSV2V_EINVAL;
     if (d.correct == 2 && !d.delta_q && d.R < d.F) return INSV2V_EINVAL;
-    const int do_step = d.latent_out != nullptr;
-    if (!do_step && !d.eps_out) return INSV2V_EINVAL;
+    if (!d.latent_out && !d.eps_out) return INSV2V_EINVAL;
     if (d.noise_on && d.noise) return INSV2V_EINVAL;   // one source of variance noise: a tensor or the stream, never both
     if (d.c_noise == 0.f) d.noise_on = 0;
+    return INSV2V_OK;
+}
+extern "C" int insv2v_cfg_step(const insv2v_step_desc* dp, insv2v_stream_t stream) {
+    if (!dp) return INSV2V_EINVAL;
+    insv2v_step_desc d = *dp;
+    if (int rc = cfg_step_check(d)) return rc;
+    const int do_step = d.latent_out != nullptr;
     int64_t n = 4ll * d.h * d.w;
     hipLaunchKernelGGL(cfg_step_kernel, dim3((unsigned)((n + 127) / 128)), dim3(128), 0, as_stream(stream), d, do_step);
+    return launch_status();
+}
+extern "C" int insv2v_cfg_step_ms(const insv2v_mstep_desc* mp, insv2v_stream_t stream) {
+    if (!mp) return INSV2V_EINVAL;
+    // insv2v_mstep_desc = the fields of insv2v_step_desc, in their order, then x0_hist and c_hist
+    static_assert(offsetof(insv2v_mstep_desc, x0_hist) == sizeof(insv2v_step_desc) &&
+                  offsetof(insv2v_mstep_desc, noise_on) == offsetof(insv2v_step_desc, noise_on) &&
+                  offsetof(insv2v_mstep_desc, branch_stride) == offsetof(insv2v_step_desc, branch_stride),
+                  "insv2v_mstep_desc must begin with the fields of insv2v_step_desc");
+    insv2v_step_desc d;
+    memcpy(&d, mp, sizeof(d));
+    if (int rc = cfg_step_check(d)) return rc;
+    const float* hist = mp->x0_hist;
+    if (!hist && mp->c_hist != 0.f) return INSV2V_EINVAL;
+    if (d.F <= 0 || d.h <= 0 || d.w <= 0) return INSV2V_EINVAL;
+    const uintptr_t bytes = (uintptr_t)(4ll * d.F * d.h * d.w) * sizeof(float), hb = (uintptr_t)hist;
+    for (uintptr_t ob : {(uintptr_t)d.latent_out, (uintptr_t)d.pred_x0, (uintptr_t)d.eps_out})   // the history is read while these are written
+        if (hb && ob && hb < ob + bytes && ob < hb + bytes) return INSV2V_EINVAL;
+    const int do_step = d.latent_out != nullptr;
+    int64_t n = 4ll * d.h * d.w;
+    // without a history this IS insv2v_cfg_step: the same kernel, so the results are bit-identical (a separate instantiation may contract
+    // its multiply-adds differently)
+    if (!hist) hipLaunchKernelGGL(cfg_step_kernel, dim3((unsigned)((n + 127) / 128)), dim3(128), 0, as_stream(stream), d, do_step);
+    else hipLaunchKernelGGL(cfg_step_ms_kernel, dim3((unsigned)((n + 127) / 128)), dim3(128), 0, as_stream(stream), d, do_step, hist, mp->c_hist);
     return launch_status();
 }
 

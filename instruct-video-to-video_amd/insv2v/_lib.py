@@ -97,6 +97,11 @@ class StepDesc(C.Structure):
                 ("branch_stride", c_i64), ("noise_seed", c_i64), ("noise_stream", c_i64), ("noise_on", c_i32)]
 
 
+class MStepDesc(C.Structure):
+    """insv2v_mstep_desc: StepDesc's fields in their order, then the multistep history term."""
+    _fields_ = StepDesc._fields_ + [("x0_hist", c_p), ("c_hist", c_f32)]
+
+
 class Im2colDesc(C.Structure):
     _fields_ = [("x", c_p), ("x2", c_p), ("out", c_p), ("ldx", c_i64), ("ldx2", c_i64), ("ldo", c_i64),
                 ("N", c_i32), ("IH", c_i32), ("IW", c_i32), ("C", c_i32), ("C1", c_i32), ("KH", c_i32), ("KW", c_i32),
@@ -140,6 +145,7 @@ SIGNATURES = {
     "insv2v_timestep_embedding": (c_i32, [c_p, c_p, c_i32, c_i32, c_f32, c_p]),
     "insv2v_build_unet_input": (c_i32, [c_p, c_p, c_p, c_p, c_f32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i64, c_i32, c_p]),
     "insv2v_cfg_step": (c_i32, [C.POINTER(StepDesc), c_p]),
+    "insv2v_cfg_step_ms": (c_i32, [C.POINTER(MStepDesc), c_p]),
     "insv2v_cfg_stats": (c_i32, [c_p, c_p, c_i32, c_i32, c_i32, c_f32, c_f32, c_i64, c_p]),
     "insv2v_warp_image": (c_i32, [c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_p]),
     "insv2v_tap_gather": (c_i32, [c_p, c_i64, c_p, c_p, c_i64, c_i32, c_i32, c_i32, c_i32, c_p]),

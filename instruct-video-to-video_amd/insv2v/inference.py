@@ -21,7 +21,7 @@ import torch
 from . import ops
 from .fused import check_operand_windows
 from .rng import stream_id, STEP
-from .schedulers import DDIMScheduler, DDPMScheduler
+from .schedulers import DDIMScheduler, DDPMScheduler, DPMSolverMultistepScheduler
 from .flow_utils import resize_flow
 
 
@@ -114,12 +114,17 @@ class GraphedUNet:
 
 class Inference:
     def __init__(self, unet, scheduler="ddim", beta_start=0.00085, beta_end=0.012, beta_schedule="scaled_linear",
-                 num_ddim_steps=20, guidance_scale=5, use_graph=True, branch_streams=True):
+                 num_ddim_steps=20, guidance_scale=5, use_graph=True, branch_streams=True, solver_order=2):
+        """``scheduler``: "ddim" / "ddpm" (the reference's two), or "dpmsolver++" / "sde-dpmsolver++": DPM-Solver++ multistep of order
+        ``solver_order`` (1 or 2; ignored by the other two) on DDIM's time grid - schedulers.DPMSolverMultistepScheduler."""
         self.unet = unet
         if scheduler == "ddim":
             cls, kw = DDIMScheduler, {"set_alpha_to_one": False, "steps_offset": 1, "clip_sample": False}
         elif scheduler == "ddpm":
             cls, kw = DDPMScheduler, {"clip_sample": False}
+        elif scheduler in ("dpmsolver++", "sde-dpmsolver++"):
+            cls, kw = DPMSolverMultistepScheduler, {"solver_order": solver_order, "algorithm_type": scheduler, "lower_order_final": True,
+                                                    "steps_offset": 1}
         else:
             raise NotImplementedError()
         self.scheduler = cls(beta_start=beta_start, beta_end=beta_end, beta_schedule=beta_schedule, **kw)
@@ -325,28 +330,39 @@ class InferenceIP2PVideo(Inference):
             ref = latent_ref[0].to(device=dev, dtype=torch.float32).contiguous()
         stats = torch.empty(2, device=dev, dtype=torch.float32) if guidance_rescale > 0 else None
         all_latent, all_pred = [], []
+        hist = t_last = None   # a multistep scheduler's history: the previous executed step's x0 prediction (kept in all_pred) and timestep
         for i, t in enumerate(self.scheduler.timesteps[start_time:]):
             t = int(t)
             ops.build_unet_input(lat, cond, runner.x_in, runner.t, t, 3)
             eps = runner.run()
-            lat, pred = self._finish_step(i, t, eps, lat, text_cfg, img_cfg, guidance_rescale, stats, ref, noise_correct_step, flows, rng=rng)
+            lat, pred = self._finish_step(i, t, eps, lat, text_cfg, img_cfg, guidance_rescale, stats, ref, noise_correct_step, flows, rng=rng,
+                                          hist=hist, t_last=t_last)
+            hist, t_last = pred, t
             all_latent.append(lat[None])
             all_pred.append(pred[None])
             yield i
         return {"latent": lat[None], "all_latent": all_latent, "all_pred": all_pred}
 
     def _finish_step(self, i, t, eps, lat, text_cfg, img_cfg, guidance_rescale, stats, ref, noise_correct_step, flows, noise=None, bstride=0,
-                     rng=None):
+                     rng=None, hist=None, t_last=None):
         """Everything of one sampling step behind the UNet for ONE clip: CFG combine (+ rescale), noise correction, scheduler
         step (inference.py:197-213, 270-277, 367-386).  eps: the clip's three branch predictions [3*F*h*w, 4] fp32, or (bstride > 0,
         the branch-major stack) a view that starts at its first branch with bstride fp32 elements between the branches.
         Variance noise of a stochastic scheduler, in order of precedence: an injected tensor (``noise`` / ``variance_noises[i]``), the
-        seeded stream of ``rng`` = (seed, unit, window) - generated inside the step kernel, no tensor -, a ``torch.randn`` draw."""
+        seeded stream of ``rng`` = (seed, unit, window) - generated inside the step kernel, no tensor -, a ``torch.randn`` draw.
+        ``hist`` / ``t_last``: the clip's x0 prediction (from the CORRECTED eps, this function's second result) and timestep of the previous
+        executed step, None on the first: what a multistep scheduler (DPM-Solver++ 2M) builds its second-order term from."""
         dev = lat.device
         F, _, h, w = lat.shape
         if stats is not None:
             ops.cfg_stats(eps, stats, F, h, w, text_cfg, img_cfg, branch_stride=bstride)
-        co = self.scheduler.coefficients(t)
+        ms = {}
+        if getattr(self.scheduler, "multistep", False):
+            co = self.scheduler.coefficients(t, t_last if hist is not None else None)
+            if co["c_hist"] != 0.0:   # (order 1 - the first executed step, the lower-order final step - is the plain step kernel)
+                ms = dict(x0_hist=hist, c_hist=co["c_hist"])
+        else:
+            co = self.scheduler.coefficients(t)
         seeded = {}
         if self.scheduler.stochastic and co["coef"][3] != 0.0:
             if noise is None:
@@ -372,10 +388,10 @@ class InferenceIP2PVideo(Inference):
             ops.cfg_step(eps, lat, nbranch=3, eps_out=eps_cfg, **common)
             dq = ops.flow_correction(eps_cfg, lat, ref, flows, co["sqrt_a"], co["sqrt_1ma"])
             ops.cfg_step(eps_cfg, lat, nbranch=0, coef=co["coef"], latent_out=new_lat, pred_x0=pred, latent_ref=ref,
-                         correct=2, delta_q=dq, noise=noise, sqrt_a=co["sqrt_a"], sqrt_1ma=co["sqrt_1ma"], **seeded)
+                         correct=2, delta_q=dq, noise=noise, sqrt_a=co["sqrt_a"], sqrt_1ma=co["sqrt_1ma"], **seeded, **ms)
         else:
             ops.cfg_step(eps, lat, nbranch=3, coef=co["coef"], latent_out=new_lat, pred_x0=pred,
-                         latent_ref=ref if correct else None, correct=1 if correct else 0, noise=noise, **seeded, **common)
+                         latent_ref=ref if correct else None, correct=1 if correct else 0, noise=noise, **seeded, **ms, **common)
         return new_lat, pred
 
     @torch.no_grad()
@@ -445,7 +461,7 @@ class InferenceIP2PVideo(Inference):
                               ncs=kw.get("noise_correct_step", 1.0) if ref is not None else 0.0,
                               text_cfg=kw.get("text_cfg", 7.5), img_cfg=kw.get("img_cfg", 1.2), gr=gr,
                               stats=torch.empty(2, device=dev, dtype=torch.float32) if gr > 0 else None,
-                              noises=kw.get("noises"), rng=_rng_of(kw), all_latent=[], all_pred=[]))
+                              noises=kw.get("noises"), rng=_rng_of(kw), all_latent=[], all_pred=[], hist=None))
         F, _, h, w = clips[0]["lat"].shape
         # BRANCH-major stack: sample br * n + c = branch br of clip c - the branches (no text, video) and (text, video), whose UNet inputs
         # are identical (inference.py:183-194), are the contiguous samples [n, 3n): the UNet computes their common prefix once (cfg_clips)
@@ -453,6 +469,7 @@ class InferenceIP2PVideo(Inference):
         runner = shared_runner(self.unet, 3 * n, F, h, w, ctx.shape[1], slot, self.use_graph, False, cfg_clips=n)
         runner.set_context(ctx)
         rows1 = F * h * w
+        t_last = None   # (the clips of a stack share start_time, so one previous timestep serves them all; the x0 history is per clip)
         for i, t in enumerate(self.scheduler.timesteps[st0:]):
             t = int(t)
             for c, cl in enumerate(clips):
@@ -462,9 +479,11 @@ class InferenceIP2PVideo(Inference):
                 noise = cl["noises"][i] if cl["noises"] is not None else None
                 cl["lat"], pred = self._finish_step(i, t, eps[c * rows1:], cl["lat"], cl["text_cfg"], cl["img_cfg"], cl["gr"],
                                                     cl["stats"], cl["ref"], cl["ncs"], cl["flows"], noise=noise, bstride=n * rows1 * 4,
-                                                    rng=cl["rng"])
+                                                    rng=cl["rng"], hist=cl["hist"], t_last=t_last)
+                cl["hist"] = pred
                 cl["all_latent"].append(cl["lat"][None])
                 cl["all_pred"].append(pred[None])
+            t_last = t
             yield
         return [{"latent": cl["lat"][None], "all_latent": cl["all_latent"], "all_pred": cl["all_pred"]} for cl in clips]
 

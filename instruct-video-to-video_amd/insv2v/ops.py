@@ -10,7 +10,7 @@ import torch
 
 from . import _lib
 from .rng import as_int64
-from ._lib import GemmDesc, GroupNormDesc, LayerNormDesc, AttentionDesc, StepDesc, FfnDesc, RowLinDesc, TattnDesc, XattnDesc, WinogradInDesc, WinogradOutDesc, check
+from ._lib import GemmDesc, GroupNormDesc, LayerNormDesc, AttentionDesc, StepDesc, MStepDesc, FfnDesc, RowLinDesc, TattnDesc, XattnDesc, WinogradInDesc, WinogradOutDesc, check
 
 ACT_NONE, ACT_SILU, ACT_GEGLU, ACT_QUICK_GELU = 0, 1, 2, 3
 ACT_RELU, ACT_SIGMOID, ACT_TANH = 4, 5, 6   # the optical-flow network's (insv2v/raft.py)
@@ -719,12 +719,41 @@ def build_unet_input(latent, img_cond, out, t_out, timestep, nbranch, branch_row
 
 def cfg_step(eps_in, latent, *, nbranch, text_cfg=1.0, img_cfg=1.0, sqrt_a=1.0, sqrt_1ma=0.0, coef=(0, 0, 0, 0),
              latent_out=None, pred_x0=None, eps_out=None, latent_ref=None, correct=0, delta_q=None, noise=None,
-             rescale_stats=None, guidance_rescale=0.0, branch_stride=0, noise_seed=None, noise_stream=0):
+             rescale_stats=None, guidance_rescale=0.0, branch_stride=0, noise_seed=None, noise_stream=0, x0_hist=None, c_hist=0.0):
     """``noise_seed`` / ``noise_stream``: the step's variance noise is generated inside the kernel from the seeded stream (element = flat
-    index of [F,4,h,w]) instead of read from ``noise``; passing both is rejected by the kernel."""
+    index of [F,4,h,w]) instead of read from ``noise``; passing both is rejected by the kernel.
+    ``x0_hist`` / ``c_hist``: the multistep term ``c_hist * x0_hist`` (the previous step's ``pred_x0``, DPM-Solver++ 2M).  Only a call
+    that gives a history goes to insv2v_cfg_step_ms (``cfg_step_ms``); every other call goes to insv2v_cfg_step as before."""
+    kw = dict(nbranch=nbranch, text_cfg=text_cfg, img_cfg=img_cfg, sqrt_a=sqrt_a, sqrt_1ma=sqrt_1ma, coef=coef, latent_out=latent_out,
+              pred_x0=pred_x0, eps_out=eps_out, latent_ref=latent_ref, correct=correct, delta_q=delta_q, noise=noise,
+              rescale_stats=rescale_stats, guidance_rescale=guidance_rescale, branch_stride=branch_stride, noise_seed=noise_seed,
+              noise_stream=noise_stream)
+    if x0_hist is not None:
+        return cfg_step_ms(eps_in, latent, x0_hist=x0_hist, c_hist=c_hist, **kw)
+    if c_hist != 0.0:
+        raise _lib.HipKernelError("cfg_step: c_hist != 0 needs x0_hist")
     lib = _lib.load()
+    d = _fill_step_desc(StepDesc(), eps_in, latent, **kw)
+    check(lib.insv2v_cfg_step(_byref(d), _stream()), "insv2v_cfg_step")
+
+
+def cfg_step_ms(eps_in, latent, *, x0_hist=None, c_hist=0.0, **kw):
+    """insv2v_cfg_step_ms: ``cfg_step`` (its keywords) plus ``c_hist * x0_hist`` in the update.  ``x0_hist`` fp32 [F,4,h,w] or None
+    (then the result is bit-identical to ``cfg_step``); it must not overlap an output."""
+    lib = _lib.load()
+    d = _fill_step_desc(MStepDesc(), eps_in, latent, **kw)
+    if x0_hist is not None and (tuple(x0_hist.shape[-4:]) != tuple(latent.shape[-4:]) or not x0_hist.is_contiguous()):
+        raise _lib.HipKernelError(f"cfg_step_ms: x0_hist {tuple(x0_hist.shape)} must be contiguous and shaped like the latent {tuple(latent.shape)}")
+    d.x0_hist = _req(x0_hist, torch.float32, "x0_hist").data_ptr() if x0_hist is not None else None
+    d.c_hist = c_hist
+    check(lib.insv2v_cfg_step_ms(_byref(d), _stream()), "insv2v_cfg_step_ms")
+
+
+def _fill_step_desc(d, eps_in, latent, *, nbranch, text_cfg=1.0, img_cfg=1.0, sqrt_a=1.0, sqrt_1ma=0.0, coef=(0, 0, 0, 0),
+                    latent_out=None, pred_x0=None, eps_out=None, latent_ref=None, correct=0, delta_q=None, noise=None,
+                    rescale_stats=None, guidance_rescale=0.0, branch_stride=0, noise_seed=None, noise_stream=0):
+    """The fields StepDesc and MStepDesc share."""
     F, _, h, w = latent.shape[-4:]
-    d = StepDesc()
     d.eps_in, d.latent = _req(eps_in, torch.float32, "eps_in").data_ptr(), _req(latent, torch.float32, "latent").data_ptr()
     d.latent_ref, d.delta_q, d.noise, d.rescale_stats = _ptr(latent_ref), _ptr(delta_q), _ptr(noise), _ptr(rescale_stats)
     d.latent_out, d.pred_x0, d.eps_out = _ptr(latent_out), _ptr(pred_x0), _ptr(eps_out)
@@ -735,7 +764,7 @@ def cfg_step(eps_in, latent, *, nbranch, text_cfg=1.0, img_cfg=1.0, sqrt_a=1.0, 
     d.guidance_rescale, d.branch_stride = guidance_rescale, branch_stride
     if noise_seed is not None:
         d.noise_seed, d.noise_stream, d.noise_on = as_int64(noise_seed), as_int64(noise_stream, "stream"), 1
-    check(lib.insv2v_cfg_step(_byref(d), _stream()), "insv2v_cfg_step")
+    return d
 
 
 def cfg_stats(eps_in, stats, F, h, w, text_cfg, img_cfg, branch_stride=0):

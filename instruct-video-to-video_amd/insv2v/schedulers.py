@@ -6,7 +6,12 @@ Only the per-step SCALAR coefficients are computed on the host (fp32, same opera
 diffusers); the tensor update runs in insv2v_cfg_step:
     x0   = (x_t - sqrt(1-a_t) eps) / sqrt(a_t)
     prev = c_x0 * x0 + c_eps * eps + c_xt * x_t + c_noise * noise
+
+DPMSolverMultistepScheduler (DPM-Solver++ 2M, Lu et al. 2022, data-prediction form; ODE and SDE) adds one term, c_hist times the x0
+prediction of the previous executed step (insv2v_cfg_step_ms).
 """
+import math
+
 import numpy as np
 import torch
 
@@ -73,3 +78,69 @@ class DDPMScheduler(_Schedule):
             c_noise = float(torch.clamp(b_prev / b_t * cur_b, min=1e-20) ** 0.5)
         return dict(sqrt_a=float(a_t ** 0.5), sqrt_1ma=float(b_t ** 0.5),
                     coef=(float((a_prev ** 0.5 * cur_b) / b_t), 0.0, float(cur_a ** 0.5 * b_prev / b_t), c_noise))
+
+
+class DPMSolverMultistepScheduler(_Schedule):
+    """DPM-Solver++ multistep, data-prediction form, orders 1 and 2 (2M), as the ODE solver ("dpmsolver++") or its SDE variant
+    ("sde-dpmsolver++"), with lower_order_final.
+
+    Time grid and end point are THIS PROJECT'S DDIMScheduler's: 'leading' spacing, steps_offset=1, and alpha_bar_prev = alpha_bar[0]
+    once prev < 0.  ``timesteps`` therefore equals DDIM's and order 1 of the ODE form IS DDIM, which ties the sampler to the goldens of
+    the unmodified reference.  The grid is a stated choice of this project, not a pin against diffusers' DPMSolverMultistepScheduler
+    (diffusers is not available where this was built; its default end point differs).
+
+    With alpha = sqrt(a), sigma = sqrt(1 - a), lambda = ln(alpha / sigma), h = lambda_prev - lambda_t, h_last = lambda_t - lambda of the
+    previous executed step, r = h_last / h and E = expm1(-h), the update prev = c_xt x_t + c_x0 x0 + c_hist x0_last + c_noise n has
+        ODE  c_xt = sigma_prev / sigma_t            c_x0 = -alpha_prev E (1 + 1/(2r))              c_hist = +alpha_prev E / (2r)          c_noise = 0
+        SDE  c_xt = sigma_prev / sigma_t e^-h       c_x0 = alpha_prev (1 - e^-2h) (1 + 1/(2r))     c_hist = -alpha_prev (1 - e^-2h) / (2r)  c_noise = sigma_prev sqrt(1 - e^-2h)
+    and order 1 is the same without the 1/(2r) terms.  Order 1 is taken on the first executed step (no history: also the first step
+    after start_time > 0), with solver_order=1, and on the last step when lower_order_final and num_inference_steps < 15.
+    The scalars are computed in float64 and handed to the kernel as fp32."""
+
+    multistep = True
+
+    def __init__(self, solver_order=2, algorithm_type="dpmsolver++", lower_order_final=True, steps_offset=1, **kw):
+        super().__init__(**kw)
+        if solver_order not in (1, 2):
+            raise NotImplementedError(f"solver_order {solver_order}")
+        if algorithm_type not in ("dpmsolver++", "sde-dpmsolver++"):
+            raise NotImplementedError(algorithm_type)
+        self.solver_order = solver_order
+        self.algorithm_type = algorithm_type
+        self.lower_order_final = lower_order_final
+        self.steps_offset = steps_offset
+        self.stochastic = algorithm_type == "sde-dpmsolver++"
+        self.final_alpha_cumprod = self.alphas_cumprod[0]
+
+    def set_timesteps(self, n):
+        self.num_inference_steps = n
+        self.timesteps = self._leading(n, self.steps_offset)
+
+    def _alpha_sigma_lambda(self, a):
+        a = float(a)
+        alpha, sigma = math.sqrt(a), math.sqrt(1.0 - a)
+        return alpha, sigma, math.log(alpha / sigma)
+
+    def coefficients(self, t, t_last=None):
+        """t_last: the timestep of the previous EXECUTED step of this trajectory, None on its first step.
+        -> dict(sqrt_a, sqrt_1ma, coef=(c_x0, 0, c_xt, c_noise), c_hist) as python floats; c_hist multiplies that step's x0."""
+        prev = t - self.num_train_timesteps // self.num_inference_steps
+        a_t = self.alphas_cumprod[t]
+        a_prev = self.alphas_cumprod[prev] if prev >= 0 else self.final_alpha_cumprod
+        _, sigma_t, lam_t = self._alpha_sigma_lambda(a_t)
+        alpha_p, sigma_p, lam_p = self._alpha_sigma_lambda(a_prev)
+        h = lam_p - lam_t
+        last = self.lower_order_final and self.num_inference_steps < 15 and t == int(self.timesteps[-1])
+        second = self.solver_order == 2 and t_last is not None and not last
+        g = 0.0   # 1 / (2r)
+        if second:
+            g = h / (2.0 * (lam_t - self._alpha_sigma_lambda(self.alphas_cumprod[t_last])[2]))
+        if self.stochastic:
+            w = -math.expm1(-2.0 * h)   # 1 - e^-2h
+            c_xt, c_x0, c_hist, c_noise = sigma_p / sigma_t * math.exp(-h), alpha_p * w * (1.0 + g), -alpha_p * w * g, sigma_p * math.sqrt(w)
+        else:
+            e = math.expm1(-h)
+            c_xt, c_x0, c_hist, c_noise = sigma_p / sigma_t, -alpha_p * e * (1.0 + g), alpha_p * e * g, 0.0
+        f32 = lambda v: float(np.float32(v))
+        return dict(sqrt_a=float(a_t ** 0.5), sqrt_1ma=float((1 - a_t) ** 0.5), coef=(f32(c_x0), 0.0, f32(c_xt), f32(c_noise)),
+                    c_hist=f32(c_hist) if second else 0.0)
