@@ -189,6 +189,10 @@ int insv2v_conv3x3_fuses_groupnorm(const insv2v_gemm_desc* d);
  * H, W of either parity ((ABI 13) odd: the last tile row / column hangs over the image, reads zeros there and stores only the pixels that exist;
  * the upsample form is exact x2 only); C a multiple of 64 (C1 too); W <= 128 (an image's 64-channel slice is staged in LDS whole, or in bands of tile rows with a
  * one-pixel halo); else INSV2V_EUNSUPPORTED and the caller uses insv2v_gemm CONV3X3.  fp16 storage of V, U, M: 6.5e-4 of max|ref| vs fp32 conv2d (profiles/r06_winograd_proto.txt).
+ * The two transforms are tested on their own, each against a float64 restatement (tests/winograd_ref.py) and bit for bit on inputs whose
+ * intermediates are fp16 numbers: tests/test_winograd_stages_gpu.py (every launch regime of the input transform - several images per
+ * workgroup with a partial last one, whole image at the LDS limit, bands with odd W, W = 128 -, strided x / x2 / residual / y / row_bias, what
+ * must stay unwritten: rows [tiles, v_group_rows) of v, columns of y beyond Cout), tests/test_winograd_stages_cpu.py (the reference itself).
  */
 typedef struct insv2v_winograd_in_desc {
     const void* x;
