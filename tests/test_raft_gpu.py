@@ -4,6 +4,8 @@ reference tree and from this image, so these tests pin HIP == oracle, and the or
 
 Stated fp16 tolerance: single kernels <= 2e-3 of max|ref| (4e-3 for the norm); the whole estimator (12 recurrent updates, fp16
 activations, fp32 correspondences) rel-RMS <= 2e-2 on the final flow, and a mean end-point error below 0.25 px at 256x384.
+Measured on an MI355X (profiles/flow_stages_pytest_gpu.txt): 0.0232 px at 256x384, 0.0175 px at 128x192, and at the sizes whose 1/8 grid is
+odd 0.0222 px at 136x184 (17x23) and 0.0200 px at 184x320 (23x40); rel-RMS 4.9e-4 ... 5.9e-4 at all four.
 """
 import math
 import os
@@ -128,10 +130,16 @@ def test_correlation_pyramid_lookup_and_upsample_vs_oracle():
     assert float(fr[:, 2:].abs().max()) == 0
 
 
-@pytest.mark.parametrize("B,H,W", [(2, 128, 192), (4, 256, 384)])
+EPE = {}               # (H, W) -> mean end-point error of this run, printed next to each other
+
+
+@pytest.mark.parametrize("B,H,W", [(2, 128, 192), (4, 256, 384), (2, 136, 184), (1, 184, 320)])
 def test_raftflow_vs_oracle(B, H, W):
     """The whole estimator as the optical-flow pipe calls it (inference.py:303-311: query frame repeated against the R reference frames):
-    key-hashed weights under torchvision's key names, frames in [-1, 1], 12 updates, the last prediction."""
+    key-hashed weights under torchvision's key names, frames in [-1, 1], 12 updates, the last prediction.  136x184 and 184x320 have odd
+    1/8 grids (17x23, 23x40): the correlation pyramid drops a row or a column at every level, InstanceNorm runs ragged chunks (the stage
+    tests of tests/test_flow_stages_gpu.py locate what fails here).  They assert the rel-RMS bound and determinism; the 0.25 px bound is
+    stated for the even sizes only."""
     from insv2v import shapes, synth
     from insv2v.raft import RAFTFlow
     from oracle.raft import RAFTFlow as OracleFlow
@@ -146,8 +154,13 @@ def test_raftflow_vs_oracle(B, H, W):
     assert tuple(got.shape) == (B, 2, H, W)
     rms = ((got.cpu() - want).pow(2).mean().sqrt() / want.pow(2).mean().sqrt()).item()
     epe = (got.cpu() - want).pow(2).sum(1).sqrt().mean().item()
-    print(f"[parity] RAFTFlow {B}x{H}x{W}: rel-rms {rms:.3e}, mean end-point error {epe:.4f} px (|flow| mean {want.abs().mean().item():.2f} px)")
-    assert math.isfinite(rms) and rms <= 2e-2 and epe <= 0.25, (rms, epe)
+    EPE[(H, W)] = epe
+    at_128 = f"{EPE[(128, 192)]:.4f} px" if (128, 192) in EPE else "not run"
+    print(f"[parity] RAFTFlow {B}x{H}x{W}: rel-rms {rms:.3e}, mean end-point error {epe:.4f} px (|flow| mean {want.abs().mean().item():.2f} px; "
+          f"end-point error at 128x192 in this run: {at_128})")
+    assert math.isfinite(rms) and rms <= 2e-2, (rms, epe)
+    if (H, W) in ((128, 192), (256, 384)):
+        assert epe <= 0.25, (rms, epe)
     # deterministic
     assert torch.equal(got, RAFTFlow(DEV, sd)(q, refs))
 
@@ -227,3 +240,53 @@ def test_optical_flow_pipe_builds_the_estimator_like_the_reference():
     rs = pipe.run_stacked([dict(latent=lat, text_cond=tc, text_uncond=tu, img_cond=cond, ref_images=imgs_r, query_images=imgs_q, **kw)] * 2)
     assert torch.equal(rs[0]["latent"], rs[1]["latent"])
     close(rs[0]["latent"], r1["latent"], 2e-2, "stacked optical-flow clip vs single")
+
+
+def test_raftflow_chunked_calls_agree_with_one_call(monkeypatch):
+    """RAFTFlow.__call__ splits its pairs by IM2COL_BUDGET_BYTES: with a budget of two pairs' 7x7-stem im2col buffers, 5 pairs at 136x184 run
+    as estimator calls of 2, 2 and 1 pairs and agree with the one-call result within the 2e-3 of the batched-vs-loop comparison."""
+    from insv2v import raft, shapes, synth
+    H, W, n = 136, 184, 5
+    est = raft.RAFTFlow(DEV, synth.synth_raft_state_dict(shapes.raft_shapes()))
+    q = synth.synth_input("raftchunk.query", (n, 3, H, W), kind="uniform")
+    r = synth.synth_input("raftchunk.refs", (n, 3, H, W), kind="uniform")
+    calls = []
+    inner = raft.RAFT.__call__
+
+    def counted(self, image1, image2, num_flow_updates=12):
+        calls.append(image1.shape[0])
+        return inner(self, image1, image2, num_flow_updates)
+    monkeypatch.setattr(raft.RAFT, "__call__", counted)
+    whole = est(q, r)
+    assert calls == [n] and tuple(whole.shape) == (n, 2, H, W)
+    del calls[:]
+    monkeypatch.setattr(raft, "IM2COL_BUDGET_BYTES", 2 * (2 * (H // 2) * (W // 2) * 784))
+    chunked = est(q, r)
+    assert calls == [2, 2, 1], calls
+    close(chunked, whole, 2e-3, "RAFTFlow in chunks of 2, 2, 1 pairs vs one call of 5")
+
+
+def test_optical_flow_pipe_at_an_odd_latent_size():
+    """InferenceIP2PVideoOpticalFlow at latent 17x23 (frames 136x184): estimating from the images equals handing the estimated flows over,
+    the flows matter, and each has the frames' size."""
+    from insv2v import shapes, synth
+    from insv2v.unet import UNet3DConditionModel
+    from insv2v.inference import InferenceIP2PVideoOpticalFlow
+    unet = UNet3DConditionModel(**synth.UNET_TINY, device=DEV).load_state_dict(synth.synth_state_dict(shapes.unet_shapes(**synth.UNET_TINY)))
+    rsd = synth.synth_raft_state_dict(shapes.raft_shapes())
+    pipe = InferenceIP2PVideoOpticalFlow(unet, scheduler="ddim", num_ddim_steps=2, raft_state_dict=rsd)
+    F_, h, w, R = 8, 17, 23, 4
+    lat, cond = synth.synth_input("rpo.lat", (1, F_, 4, h, w)), synth.synth_input("rpo.cond", (1, F_, 4, h, w))
+    tc, tu = synth.synth_input("rpo.tc", (1, 77, 64)), synth.synth_input("rpo.tu", (1, 77, 64))
+    lref = synth.synth_input("rpo.lref", (1, R, 4, h, w))
+    imgs_r = synth.synth_input("rpo.ir", (1, R, 3, 8 * h, 8 * w), kind="uniform").to(DEV)
+    imgs_q = synth.synth_input("rpo.iq", (1, F_ - R, 3, 8 * h, 8 * w), kind="uniform").to(DEV)
+    kw = dict(latent_ref=lref, noise_correct_step=0.5, text_cfg=7.5, img_cfg=1.5)
+    r1 = pipe.second_clip_forward(lat, tc, tu, cond, ref_images=imgs_r, query_images=imgs_q, **kw)
+    flows = pipe.obtain_flow_batched(imgs_r[0], imgs_q[0])
+    assert len(flows) == F_ - R and all(tuple(f.shape) == (R, 2, 136, 184) for f in flows)
+    r2 = pipe.second_clip_forward(lat, tc, tu, cond, flows=flows, **kw)
+    assert tuple(r1["latent"].shape[-2:]) == (h, w) and torch.isfinite(r1["latent"]).all()
+    assert torch.equal(r1["latent"], r2["latent"])
+    r0 = pipe.second_clip_forward(lat, tc, tu, cond, flows=[torch.zeros_like(f) for f in flows], **kw)
+    assert (r0["latent"] - r1["latent"]).abs().max() > 1e-3, "the estimated flows must matter"
