@@ -557,6 +557,60 @@ typedef struct insv2v_mstep_desc {
     float c_hist;
 } insv2v_mstep_desc;
 int insv2v_cfg_step_ms(const insv2v_mstep_desc* d, insv2v_stream_t stream);
+/*
+ * Masked form of insv2v_cfg_step_ms (localized and partial edits): the same kernel body with one more pass behind the scheduler update,
+ * which holds the region outside the mask at the source video's latent re-noised to the level the step's output lives at:
+ *   known      = k_src*src + k_noise*known_noise            (k_src = sqrt(alpha_bar_prev), k_noise = sqrt(1 - alpha_bar_prev))
+ *   latent_out = mask*prev + (1 - mask)*known               (mask 1 = edit, 0 = keep; broadcast over the 4 channels)
+ * pred_x0 and eps_out stay the model's own (unblended), so the multistep history keeps reading the model's prediction.  Everything in
+ * front of the blend - CFG combine, guidance rescale, correction modes, nbranch, branch_stride, injected / seeded variance noise, the
+ * history term - is insv2v_cfg_step_ms's.  With mask == NULL the call IS insv2v_cfg_step_ms (the same kernels: bit-identical results).
+ * The descriptor holds the fields of insv2v_mstep_desc in their order, then:
+ *   mask         fp32 [F,h,w] in [0,1] or NULL
+ *   src          fp32 [F,4,h,w]: the scaled source latent (what the VAE encoder returns times the scale factor)
+ *   known_noise  fp32 [F,4,h,w]: the fixed noise the source is re-noised with (the window's initial noise)
+ *   k_src, k_noise
+ * INSV2V_EINVAL: a mask without src or known_noise; a mask with latent_out == NULL; F, h or w <= 0; mask, src, known_noise or x0_hist
+ * overlapping the range of latent_out, pred_x0 or eps_out (they are read while those are written).
+ * An addition to ABI 14: the existing descriptors and entries are unchanged.
+ */
+typedef struct insv2v_maskstep_desc {
+    const float* eps_in;
+    const float* latent;
+    const float* latent_ref;
+    const float* delta_q;
+    const float* noise;
+    const float* rescale_stats;
+    float* latent_out;
+    float* pred_x0;
+    float* eps_out;
+    int32_t nbranch, F, h, w, R;
+    int32_t correct;
+    float text_cfg, img_cfg;
+    float sqrt_a, sqrt_1ma;
+    float c_x0, c_eps, c_xt, c_noise;
+    float guidance_rescale;
+    int64_t branch_stride;
+    int64_t noise_seed, noise_stream;
+    int32_t noise_on;
+    const float* x0_hist;
+    float c_hist;
+    const float* mask;
+    const float* src;
+    const float* known_noise;
+    float k_src, k_noise;
+} insv2v_maskstep_desc;
+int insv2v_cfg_step_mask(const insv2v_maskstep_desc* d, insv2v_stream_t stream);
+/* Image-resolution mask fp32 [N,H,W] -> latent resolution [N,H/8,W/8]: per 8x8 cell its mean (mode 0; a pairwise sum, so a mask in
+ * [0,1] is within 6 * 2^-24 of the exact mean) or its maximum (mode 1).  H and W must be positive multiples of 8 (any such size);
+ * everything else returns INSV2V_EINVAL. */
+int insv2v_mask_to_latent(const float* mask, float* out, int32_t N, int32_t H, int32_t W, int32_t mode, insv2v_stream_t stream);
+/* out = clip(mask*edited + (1 - mask)*original, -1, 1) on fp32 [N,3,H,W] frames, mask fp32 [N,H,W] at image resolution (broadcast over
+ * the channels).  out may alias edited (each element is read before it is written, by the same thread). */
+int insv2v_composite(const float* edited, const float* original, const float* mask, float* out, int32_t N, int32_t H, int32_t W,
+                     insv2v_stream_t stream);
+/* out = ka*z + kb*noise over n fp32 elements (the source latent re-noised to a step's level; out may alias z or noise). */
+int insv2v_add_noise(const float* z, const float* noise, float* out, int64_t n, float ka, float kb, insv2v_stream_t stream);
 /* std over all elements of n1 (branch 1) and of the CFG-combined eps -> stats[0..1] (inference.py:18-19). */
 int insv2v_cfg_stats(const float* eps_in, float* stats, int32_t F, int32_t h, int32_t w, float text_cfg,
                      float img_cfg, int64_t branch_stride, insv2v_stream_t stream);

@@ -84,8 +84,17 @@ __device__ __forceinline__ float cfg_eps(const insv2v_step_desc& p, int f, int c
 
 // one thread per (c,y,x); loops over frames so the mean over reference frames is thread-local.
 // MS: the multistep form (insv2v_cfg_step_ms) - one more term, c_hist times the previous step's x0 prediction; everything else is shared.
-template <bool MS>
-__device__ __forceinline__ void cfg_step_body(const insv2v_step_desc& p, int do_step, const float* x0_hist, float c_hist) {
+// MASK: the masked form (insv2v_cfg_step_mask) - behind the update, latent_out is blended with the re-noised source latent; pred_x0 and
+// eps_out stay the model's own.
+struct cfg_mask_args {
+    const float* mask;         // [F,h,w]
+    const float* src;          // [F,4,h,w]
+    const float* known_noise;  // [F,4,h,w]
+    float k_src, k_noise;
+};
+template <bool MS, bool MASK = false>
+__device__ __forceinline__ void cfg_step_body(const insv2v_step_desc& p, int do_step, const float* x0_hist, float c_hist,
+                                              const cfg_mask_args& mk = cfg_mask_args{}) {
     const int64_t hw = (int64_t)p.h * p.w;
     int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= 4 * hw) return;
@@ -125,6 +134,11 @@ __device__ __forceinline__ void cfg_step_body(const insv2v_step_desc& p, int do_
             if (p.noise) prev += p.c_noise * p.noise[li];
             else if (p.noise_on) prev += p.c_noise * rng_normal_at(p.noise_seed, p.noise_stream, li);
             if (p.pred_x0) p.pred_x0[li] = x0;
+            if constexpr (MASK) {
+                const float m = mk.mask[(int64_t)f * hw + r];
+                const float known = mk.k_src * mk.src[li] + mk.k_noise * mk.known_noise[li];
+                prev = m * prev + (1.f - m) * known;   // m == 0: exactly `known`, whatever the model predicted
+            }
             p.latent_out[li] = prev;
         }
     }
@@ -132,6 +146,10 @@ __device__ __forceinline__ void cfg_step_body(const insv2v_step_desc& p, int do_
 __global__ void cfg_step_kernel(insv2v_step_desc p, int do_step) { cfg_step_body<false>(p, do_step, nullptr, 0.f); }
 __global__ void cfg_step_ms_kernel(insv2v_step_desc p, int do_step, const float* x0_hist, float c_hist) {
     cfg_step_body<true>(p, do_step, x0_hist, c_hist);
+}
+template <bool MS>
+__global__ void cfg_step_mask_kernel(insv2v_step_desc p, int do_step, const float* x0_hist, float c_hist, cfg_mask_args mk) {
+    cfg_step_body<MS, true>(p, do_step, x0_hist, c_hist, mk);
 }
 // argument checks shared by both entry points; normalises d in place
 static int cfg_step_check(insv2v_step_desc& d) {
@@ -176,6 +194,101 @@ extern "C" int insv2v_cfg_step_ms(const insv2v_mstep_desc* mp, insv2v_stream_t s
     // its multiply-adds differently)
     if (!hist) hipLaunchKernelGGL(cfg_step_kernel, dim3((unsigned)((n + 127) / 128)), dim3(128), 0, as_stream(stream), d, do_step);
     else hipLaunchKernelGGL(cfg_step_ms_kernel, dim3((unsigned)((n + 127) / 128)), dim3(128), 0, as_stream(stream), d, do_step, hist, mp->c_hist);
+    return launch_status();
+}
+extern "C" int insv2v_cfg_step_mask(const insv2v_maskstep_desc* kp, insv2v_stream_t stream) {
+    if (!kp) return INSV2V_EINVAL;
+    // insv2v_maskstep_desc = the fields of insv2v_mstep_desc, in their order, then mask, src, known_noise, k_src and k_noise
+    static_assert(offsetof(insv2v_maskstep_desc, mask) == sizeof(insv2v_mstep_desc) &&
+                  offsetof(insv2v_maskstep_desc, x0_hist) == offsetof(insv2v_mstep_desc, x0_hist) &&
+                  offsetof(insv2v_maskstep_desc, c_hist) == offsetof(insv2v_mstep_desc, c_hist) &&
+                  offsetof(insv2v_maskstep_desc, noise_on) == offsetof(insv2v_mstep_desc, noise_on) &&
+                  offsetof(insv2v_maskstep_desc, branch_stride) == offsetof(insv2v_mstep_desc, branch_stride),
+                  "insv2v_maskstep_desc must begin with the fields of insv2v_mstep_desc");
+    insv2v_mstep_desc m;
+    memcpy(&m, kp, sizeof(m));
+    // without a mask this IS insv2v_cfg_step_ms (and, without a history, insv2v_cfg_step): the same kernels, so the results are
+    // bit-identical - a dispatch and not a runtime `if`, for the reason given there
+    if (!kp->mask) return insv2v_cfg_step_ms(&m, stream);
+    insv2v_step_desc d;
+    memcpy(&d, kp, sizeof(d));
+    if (int rc = cfg_step_check(d)) return rc;
+    if (!kp->src || !kp->known_noise || !d.latent_out) return INSV2V_EINVAL;
+    const float* hist = kp->x0_hist;
+    if (!hist && kp->c_hist != 0.f) return INSV2V_EINVAL;
+    if (d.F <= 0 || d.h <= 0 || d.w <= 0) return INSV2V_EINVAL;
+    const uintptr_t bytes = (uintptr_t)(4ll * d.F * d.h * d.w) * sizeof(float);
+    const struct { uintptr_t b, n; } reads[] = {{(uintptr_t)kp->mask, bytes / 4}, {(uintptr_t)kp->src, bytes}, {(uintptr_t)kp->known_noise, bytes},
+                                                {(uintptr_t)hist, bytes}};
+    for (uintptr_t ob : {(uintptr_t)d.latent_out, (uintptr_t)d.pred_x0, (uintptr_t)d.eps_out})   // these are read while the outputs are written
+        for (const auto& rd : reads)
+            if (rd.b && ob && rd.b < ob + bytes && ob < rd.b + rd.n) return INSV2V_EINVAL;
+    const cfg_mask_args mk{kp->mask, kp->src, kp->known_noise, kp->k_src, kp->k_noise};
+    const int64_t n = 4ll * d.h * d.w;
+    const dim3 grid((unsigned)((n + 127) / 128));
+    if (!hist) hipLaunchKernelGGL(cfg_step_mask_kernel<false>, grid, dim3(128), 0, as_stream(stream), d, 1, (const float*)nullptr, 0.f, mk);
+    else hipLaunchKernelGGL(cfg_step_mask_kernel<true>, grid, dim3(128), 0, as_stream(stream), d, 1, hist, kp->c_hist, mk);
+    return launch_status();
+}
+
+// ---- masks (localized edits): image-resolution mask -> latent resolution, the final composite, and the re-noised source latent
+__device__ __forceinline__ float mask_tree8(const float* v, int mode) {   // pairwise: 3 roundings per level of 8, not 7
+    if (mode) return fmaxf(fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3])), fmaxf(fmaxf(v[4], v[5]), fmaxf(v[6], v[7])));
+    return ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7]));
+}
+__global__ __launch_bounds__(256) void mask_to_latent_kernel(const float* __restrict__ mask, float* __restrict__ out, int64_t total, int h, int w, int mode) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;   // over [N, h, w] cells
+    if (i >= total) return;
+    const int x = (int)(i % w);
+    const int64_t ny = i / w;                                     // n * h + y: the cell's first image row is 8 * ny
+    const float* cell = mask + (ny * 8) * ((int64_t)w * 8) + (int64_t)x * 8;
+    float rows[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        float v[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) v[k] = cell[(int64_t)j * w * 8 + k];
+        rows[j] = mask_tree8(v, mode);
+    }
+    const float s = mask_tree8(rows, mode);
+    out[i] = mode ? s : s * 0.015625f;
+}
+extern "C" int insv2v_mask_to_latent(const float* mask, float* out, int32_t N, int32_t H, int32_t W, int32_t mode, insv2v_stream_t stream) {
+    if (!mask || !out || N <= 0 || H <= 0 || W <= 0 || (H & 7) || (W & 7) || (mode != 0 && mode != 1)) return INSV2V_EINVAL;
+    const int64_t total = (int64_t)N * (H / 8) * (W / 8);
+    const int64_t grid = (total + 255) / 256;
+    if (grid > 0x7fffffffll) return INSV2V_EINVAL;
+    hipLaunchKernelGGL(mask_to_latent_kernel, dim3((unsigned)grid), dim3(256), 0, as_stream(stream), mask, out, total, H / 8, W / 8, (int)mode);
+    return launch_status();
+}
+// (no __restrict__: out may be edited)
+__global__ __launch_bounds__(256) void composite_kernel(const float* edited, const float* original, const float* mask, float* out, int64_t total, int64_t hw) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;   // over [N,3,H,W]
+    if (i >= total) return;
+    const int64_t nc = i / hw;
+    const float m = mask[(nc / 3) * hw + (i - nc * hw)];
+    const float v = m * edited[i] + (1.f - m) * original[i];
+    out[i] = fminf(fmaxf(v, -1.f), 1.f);
+}
+extern "C" int insv2v_composite(const float* edited, const float* original, const float* mask, float* out, int32_t N, int32_t H, int32_t W,
+                                insv2v_stream_t stream) {
+    if (!edited || !original || !mask || !out || N <= 0 || H <= 0 || W <= 0) return INSV2V_EINVAL;
+    const int64_t hw = (int64_t)H * W, total = 3 * (int64_t)N * hw;
+    const int64_t grid = (total + 255) / 256;
+    if (grid > 0x7fffffffll) return INSV2V_EINVAL;
+    hipLaunchKernelGGL(composite_kernel, dim3((unsigned)grid), dim3(256), 0, as_stream(stream), edited, original, mask, out, total, hw);
+    return launch_status();
+}
+__global__ __launch_bounds__(256) void add_noise_kernel(const float* z, const float* noise, float* out, int64_t n, float ka, float kb) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) out[i] = ka * z[i] + kb * noise[i];
+}
+extern "C" int insv2v_add_noise(const float* z, const float* noise, float* out, int64_t n, float ka, float kb, insv2v_stream_t stream) {
+    if (!z || !noise || !out || n < 0) return INSV2V_EINVAL;
+    if (n == 0) return INSV2V_OK;
+    const int64_t grid = (n + 255) / 256;
+    if (grid > 0x7fffffffll) return INSV2V_EINVAL;
+    hipLaunchKernelGGL(add_noise_kernel, dim3((unsigned)grid), dim3(256), 0, as_stream(stream), z, noise, out, n, ka, kb);
     return launch_status();
 }
 

@@ -102,6 +102,11 @@ class MStepDesc(C.Structure):
     _fields_ = StepDesc._fields_ + [("x0_hist", c_p), ("c_hist", c_f32)]
 
 
+class MaskStepDesc(C.Structure):
+    """insv2v_maskstep_desc: MStepDesc's fields in their order, then the known region (mask, source latent, its noise and coefficients)."""
+    _fields_ = MStepDesc._fields_ + [("mask", c_p), ("src", c_p), ("known_noise", c_p), ("k_src", c_f32), ("k_noise", c_f32)]
+
+
 class Im2colDesc(C.Structure):
     _fields_ = [("x", c_p), ("x2", c_p), ("out", c_p), ("ldx", c_i64), ("ldx2", c_i64), ("ldo", c_i64),
                 ("N", c_i32), ("IH", c_i32), ("IW", c_i32), ("C", c_i32), ("C1", c_i32), ("KH", c_i32), ("KW", c_i32),
@@ -146,6 +151,10 @@ SIGNATURES = {
     "insv2v_build_unet_input": (c_i32, [c_p, c_p, c_p, c_p, c_f32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i64, c_i32, c_p]),
     "insv2v_cfg_step": (c_i32, [C.POINTER(StepDesc), c_p]),
     "insv2v_cfg_step_ms": (c_i32, [C.POINTER(MStepDesc), c_p]),
+    "insv2v_cfg_step_mask": (c_i32, [C.POINTER(MaskStepDesc), c_p]),
+    "insv2v_mask_to_latent": (c_i32, [c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_p]),
+    "insv2v_composite": (c_i32, [c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_p]),
+    "insv2v_add_noise": (c_i32, [c_p, c_p, c_p, c_i64, c_f32, c_f32, c_p]),
     "insv2v_cfg_stats": (c_i32, [c_p, c_p, c_i32, c_i32, c_i32, c_f32, c_f32, c_i64, c_p]),
     "insv2v_warp_image": (c_i32, [c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_p]),
     "insv2v_tap_gather": (c_i32, [c_p, c_i64, c_p, c_p, c_i64, c_i32, c_i32, c_i32, c_i32, c_p]),

@@ -277,9 +277,37 @@ def _rng_of(kw):
     return (kw["seed"], kw.get("unit", 0), kw.get("window", 0))
 
 
+def check_known_region(latent, mask=None, source_latent=None, known_noise=None):
+    """Host-side check of a call's masked-edit arguments (no launch): ``mask`` [1,F,h,w] at latent resolution, ``source_latent`` and
+    ``known_noise`` [1,F,4,h,w] like ``latent``; a mask needs both of the others, and they mean nothing without one."""
+    if mask is None:
+        if source_latent is not None or known_noise is not None:
+            raise ValueError("source_latent / known_noise are the known region of a masked edit: pass mask= with them")
+        return
+    if source_latent is None or known_noise is None:
+        raise ValueError("a mask needs source_latent= (the scaled source latent) and known_noise= (the window's initial noise)")
+    b, F, _, h, w = latent.shape
+    if not torch.is_tensor(mask) or tuple(mask.shape) != (b, F, h, w):
+        raise ValueError(f"mask {tuple(getattr(mask, 'shape', ()))} must be [{b},{F},{h},{w}]: one latent-resolution plane per frame of latent {tuple(latent.shape)}")
+    for name, t in (("source_latent", source_latent), ("known_noise", known_noise)):
+        if not torch.is_tensor(t) or tuple(t.shape) != tuple(latent.shape):
+            raise ValueError(f"{name} {tuple(getattr(t, 'shape', ()))} must be shaped like the latent {tuple(latent.shape)}")
+
+
+_KNOWN_KEYS = ("mask", "source_latent", "known_noise")
+
+
 class InferenceIP2PVideo(Inference):
     def zeros(self, x):
         return torch.zeros_like(x)
+
+    def _known_tensors(self, latent, mask=None, source_latent=None, known_noise=None):
+        """The known region of ONE clip on the device - dict(mask [F,h,w], src [F,4,h,w], noise [F,4,h,w]) - or None without a mask.
+        The public entry points have checked it (``check_known_region``)."""
+        if mask is None:
+            return None
+        to = lambda t: t[0].to(device=self.unet.device, dtype=torch.float32).contiguous()
+        return dict(mask=to(mask), src=to(source_latent), noise=to(known_noise))
 
     # ---- shared loop ------------------------------------------------------------------------------
     def _clip_tensors(self, latent, img_cond):
@@ -318,10 +346,12 @@ class InferenceIP2PVideo(Inference):
             return done.value
 
     def _loop_gen(self, latent, text_cond, text_uncond, img_cond, text_cfg, img_cfg, start_time, guidance_rescale,
-                  latent_ref=None, noise_correct_step=0.0, flows=None, slot=0, rng=None):
+                  latent_ref=None, noise_correct_step=0.0, flows=None, slot=0, rng=None, known=None):
         """One sampling loop as a generator that yields after enqueueing each step's (asynchronous) GPU work,
         so several independent clips can be interleaved from one host thread (``run_concurrent``).
-        ``rng`` = (seed, unit, window) or None: where a stochastic scheduler's variance noise comes from (``_finish_step``)."""
+        ``rng`` = (seed, unit, window) or None: where a stochastic scheduler's variance noise comes from (``_finish_step``).
+        ``known`` = (mask, source_latent, known_noise) or None: the known region of a masked edit (``_finish_step``)."""
+        known = self._known_tensors(latent, *known) if known is not None else None
         lat, cond, runner = self._prep(latent, text_cond, text_uncond, img_cond, slot)
         dev = lat.device
         F, _, h, w = lat.shape
@@ -336,7 +366,7 @@ class InferenceIP2PVideo(Inference):
             ops.build_unet_input(lat, cond, runner.x_in, runner.t, t, 3)
             eps = runner.run()
             lat, pred = self._finish_step(i, t, eps, lat, text_cfg, img_cfg, guidance_rescale, stats, ref, noise_correct_step, flows, rng=rng,
-                                          hist=hist, t_last=t_last)
+                                          hist=hist, t_last=t_last, known=known)
             hist, t_last = pred, t
             all_latent.append(lat[None])
             all_pred.append(pred[None])
@@ -344,14 +374,17 @@ class InferenceIP2PVideo(Inference):
         return {"latent": lat[None], "all_latent": all_latent, "all_pred": all_pred}
 
     def _finish_step(self, i, t, eps, lat, text_cfg, img_cfg, guidance_rescale, stats, ref, noise_correct_step, flows, noise=None, bstride=0,
-                     rng=None, hist=None, t_last=None):
+                     rng=None, hist=None, t_last=None, known=None):
         """Everything of one sampling step behind the UNet for ONE clip: CFG combine (+ rescale), noise correction, scheduler
         step (inference.py:197-213, 270-277, 367-386).  eps: the clip's three branch predictions [3*F*h*w, 4] fp32, or (bstride > 0,
         the branch-major stack) a view that starts at its first branch with bstride fp32 elements between the branches.
         Variance noise of a stochastic scheduler, in order of precedence: an injected tensor (``noise`` / ``variance_noises[i]``), the
         seeded stream of ``rng`` = (seed, unit, window) - generated inside the step kernel, no tensor -, a ``torch.randn`` draw.
         ``hist`` / ``t_last``: the clip's x0 prediction (from the CORRECTED eps, this function's second result) and timestep of the previous
-        executed step, None on the first: what a multistep scheduler (DPM-Solver++ 2M) builds its second-order term from."""
+        executed step, None on the first: what a multistep scheduler (DPM-Solver++ 2M) builds its second-order term from.
+        ``known`` (``_known_tensors``): a masked edit - inside the step kernel the new latent becomes
+        ``mask * prev + (1 - mask) * (k_src * src + k_noise * noise)`` with the scheduler's ``known_coefficients(t)``; the x0 prediction
+        stays the model's own.  None: the launches of an unmasked call, unchanged."""
         dev = lat.device
         F, _, h, w = lat.shape
         if stats is not None:
@@ -378,6 +411,9 @@ class InferenceIP2PVideo(Inference):
                     noise = torch.randn(lat.shape, device=dev, dtype=torch.float32)
         else:
             noise = None
+        if known is not None:
+            k_src, k_noise = self.scheduler.known_coefficients(t)
+            ms = dict(ms, mask=known["mask"], src=known["src"], known_noise=known["noise"], k_src=k_src, k_noise=k_noise)
         new_lat, pred = torch.empty_like(lat), torch.empty_like(lat)
         correct = ref is not None and noise_correct_step * self.num_ddim_steps > i
         common = dict(text_cfg=text_cfg, img_cfg=img_cfg, sqrt_a=co["sqrt_a"], sqrt_1ma=co["sqrt_1ma"],
@@ -400,7 +436,8 @@ class InferenceIP2PVideo(Inference):
         ``run_concurrent``) as ONE batch: the 3 CFG branches of all n clips are stacked into every UNet launch
         (B = 3n; statistics stay per sample), so weights are read once per group of clips, every launch fills the chip
         and the lowest UNet levels need no split-K.  All clips must share shapes, ``start_time`` and the scheduler;
-        guidance scales may differ.  A call's ``seed`` / ``unit`` / ``window`` select its seeded noise streams as in ``__call__``: a unit's
+        guidance scales may differ; each clip may or may not carry a known region (``mask`` / ``source_latent`` / ``known_noise``, as for
+        ``__call__``).  A call's ``seed`` / ``unit`` / ``window`` select its seeded noise streams as in ``__call__``: a unit's
         result then does not depend on what it is stacked with.  Also the path of a batched ``__call__`` (inference.py:183-187 works for any b).
         (Round 4 measured two stacks of 5 clips running concurrently on two HIP streams against one stack of 10: 14.02 vs 14.50 frames/s -
         the persistent kernels own every CU, a second chain only fills tails and pays for it with half-sized launches.)
@@ -410,6 +447,8 @@ class InferenceIP2PVideo(Inference):
         n = len(calls)
         if n == 0:
             return []
+        for kw in calls:   # a malformed known region is refused before the first launch of the first chain
+            check_known_region(kw["latent"], *(kw.get(k) for k in _KNOWN_KEYS))
         gen = self._stacked_gen(calls, 0, max_clips)
         while True:
             try:
@@ -461,7 +500,8 @@ class InferenceIP2PVideo(Inference):
                               ncs=kw.get("noise_correct_step", 1.0) if ref is not None else 0.0,
                               text_cfg=kw.get("text_cfg", 7.5), img_cfg=kw.get("img_cfg", 1.2), gr=gr,
                               stats=torch.empty(2, device=dev, dtype=torch.float32) if gr > 0 else None,
-                              noises=kw.get("noises"), rng=_rng_of(kw), all_latent=[], all_pred=[], hist=None))
+                              noises=kw.get("noises"), rng=_rng_of(kw), all_latent=[], all_pred=[], hist=None,
+                              known=self._known_tensors(kw["latent"], *(kw.get(k) for k in _KNOWN_KEYS))))
         F, _, h, w = clips[0]["lat"].shape
         # BRANCH-major stack: sample br * n + c = branch br of clip c - the branches (no text, video) and (text, video), whose UNet inputs
         # are identical (inference.py:183-194), are the contiguous samples [n, 3n): the UNet computes their common prefix once (cfg_clips)
@@ -479,7 +519,7 @@ class InferenceIP2PVideo(Inference):
                 noise = cl["noises"][i] if cl["noises"] is not None else None
                 cl["lat"], pred = self._finish_step(i, t, eps[c * rows1:], cl["lat"], cl["text_cfg"], cl["img_cfg"], cl["gr"],
                                                     cl["stats"], cl["ref"], cl["ncs"], cl["flows"], noise=noise, bstride=n * rows1 * 4,
-                                                    rng=cl["rng"], hist=cl["hist"], t_last=t_last)
+                                                    rng=cl["rng"], hist=cl["hist"], t_last=t_last, known=cl["known"])
                 cl["hist"] = pred
                 cl["all_latent"].append(cl["lat"][None])
                 cl["all_pred"].append(pred[None])
@@ -492,6 +532,7 @@ class InferenceIP2PVideo(Inference):
         ``run_stacked``.  A stochastic scheduler draws ONE [b,F,4,h,w] normal per step like the reference and slices it - or, with
         ``seed``, batch entry j takes the streams of unit ``unit`` + j."""
         b = latent.shape[0]
+        check_known_region(latent, *(kw.get(k) for k in _KNOWN_KEYS))   # (before the noise draws below: nothing is launched for a malformed call)
         noises = None
         seed, unit = kw.pop("seed", None), kw.pop("unit", 0)
         if seed is not None:
@@ -509,7 +550,7 @@ class InferenceIP2PVideo(Inference):
             c = dict(kw, latent=latent[j:j + 1], text_cond=text_cond[j:j + 1], text_uncond=text_uncond[j:j + 1], img_cond=img_cond[j:j + 1])
             if latent_ref is not None:
                 c["latent_ref"] = latent_ref[j:j + 1]
-            for k in ("ref_images", "query_images"):   # (the optical-flow pipe's batched form: one estimator pass per batch entry)
+            for k in ("ref_images", "query_images") + _KNOWN_KEYS:   # (the optical-flow pipe's batched form: one estimator pass per batch entry; a batched known region: one slice per entry)
                 if kw.get(k) is not None:
                     c[k] = kw[k][j:j + 1]
             if noises is not None:
@@ -531,6 +572,8 @@ class InferenceIP2PVideo(Inference):
         different clips (units are independent: insv2v_run_loveu_tgve.py:83,101).  Returns the result dicts."""
         if not hasattr(self, "_slot_streams"):
             self._slot_streams = {}
+        for kw in calls:   # a malformed known region is refused before the first launch
+            check_known_region(kw["latent"], *(kw.get(k) for k in _KNOWN_KEYS))
         main = torch.cuda.current_stream()
         gens = []
         for slot, kw in enumerate(calls):
@@ -539,7 +582,8 @@ class InferenceIP2PVideo(Inference):
             st.wait_stream(main)
             args = dict(latent=kw["latent"], text_cond=kw["text_cond"], text_uncond=kw["text_uncond"], img_cond=kw["img_cond"],
                         text_cfg=kw.get("text_cfg", 7.5), img_cfg=kw.get("img_cfg", 1.2), start_time=kw.get("start_time", 0),
-                        guidance_rescale=kw.get("guidance_rescale", 0.0), slot=slot, rng=_rng_of(kw))
+                        guidance_rescale=kw.get("guidance_rescale", 0.0), slot=slot, rng=_rng_of(kw),
+                        known=tuple(kw.get(k) for k in _KNOWN_KEYS) if kw.get("mask") is not None else None)
             if kw.get("latent_ref") is not None:
                 args.update(latent_ref=kw["latent_ref"], noise_correct_step=kw.get("noise_correct_step", 1.0))
             gens.append((st, self._loop_gen(**args)))
@@ -561,25 +605,35 @@ class InferenceIP2PVideo(Inference):
     # ---- reference call surface ----------------------------------------------------------------------
     @torch.no_grad()
     def __call__(self, latent, text_cond, text_uncond, img_cond, text_cfg=7.5, img_cfg=1.2, start_time=0,
-                 guidance_rescale=0.0, seed=None, unit=0, window=0):
-        """``seed`` (default None: the draws of ``torch.randn``, as before): a stochastic scheduler's variance noise of step i comes from
+                 guidance_rescale=0.0, seed=None, unit=0, window=0, mask=None, source_latent=None, known_noise=None):
+        """``mask`` [1,F,h,w] in [0,1] at latent resolution (1 = edit, 0 = keep) with ``source_latent`` [1,F,4,h,w] (the SCALED source
+        latent, ``model.encode_image_to_latent``'s result) and ``known_noise`` [1,F,4,h,w] (the fixed noise it is re-noised with: the
+        window's initial noise): after every step the latent outside the mask is the source's, re-noised to that step's level - inside
+        the step kernel, no extra launch.  Without a mask the call launches exactly what it launched before.
+        ``seed`` (default None: the draws of ``torch.randn``, as before): a stochastic scheduler's variance noise of step i comes from
         the seeded stream ``rng.stream_id(STEP, unit, window, i)`` - a pure function of (seed, unit, window, step, element), whatever
         else runs.  Injected ``variance_noises`` win over it; a deterministic scheduler ignores it."""
         if latent.shape[0] != 1:
             return self._batched_call(latent, text_cond, text_uncond, img_cond, text_cfg=text_cfg, img_cfg=img_cfg, start_time=start_time,
-                                      guidance_rescale=guidance_rescale, seed=seed, unit=unit, window=window)
+                                      guidance_rescale=guidance_rescale, seed=seed, unit=unit, window=window,
+                                      mask=mask, source_latent=source_latent, known_noise=known_noise)
+        check_known_region(latent, mask, source_latent, known_noise)
         return self._loop(latent, text_cond, text_uncond, img_cond, text_cfg, img_cfg, start_time, guidance_rescale,
-                          rng=_rng_of(dict(seed=seed, unit=unit, window=window)))
+                          rng=_rng_of(dict(seed=seed, unit=unit, window=window)),
+                          known=(mask, source_latent, known_noise) if mask is not None else None)
 
     @torch.no_grad()
     def second_clip_forward(self, latent, text_cond, text_uncond, img_cond, latent_ref, noise_correct_step=1.0,
-                            text_cfg=7.5, img_cfg=1.2, start_time=0, guidance_rescale=0.0, seed=None, unit=0, window=0):
+                            text_cfg=7.5, img_cfg=1.2, start_time=0, guidance_rescale=0.0, seed=None, unit=0, window=0,
+                            mask=None, source_latent=None, known_noise=None):
         if latent.shape[0] != 1:
             return self._batched_call(latent, text_cond, text_uncond, img_cond, latent_ref=latent_ref, noise_correct_step=noise_correct_step,
                                       text_cfg=text_cfg, img_cfg=img_cfg, start_time=start_time, guidance_rescale=guidance_rescale,
-                                      seed=seed, unit=unit, window=window)
+                                      seed=seed, unit=unit, window=window, mask=mask, source_latent=source_latent, known_noise=known_noise)
+        check_known_region(latent, mask, source_latent, known_noise)
         return self._loop(latent, text_cond, text_uncond, img_cond, text_cfg, img_cfg, start_time, guidance_rescale,
-                          latent_ref=latent_ref, noise_correct_step=noise_correct_step, rng=_rng_of(dict(seed=seed, unit=unit, window=window)))
+                          latent_ref=latent_ref, noise_correct_step=noise_correct_step, rng=_rng_of(dict(seed=seed, unit=unit, window=window)),
+                          known=(mask, source_latent, known_noise) if mask is not None else None)
 
 
 class InferenceIP2PVideoOpticalFlow(InferenceIP2PVideo):
@@ -620,7 +674,8 @@ class InferenceIP2PVideoOpticalFlow(InferenceIP2PVideo):
     @torch.no_grad()
     def second_clip_forward(self, latent, text_cond, text_uncond, img_cond, latent_ref, ref_images=None,
                             query_images=None, noise_correct_step=1.0, text_cfg=7.5, img_cfg=1.2, start_time=0,
-                            guidance_rescale=0.0, flows=None, seed=None, unit=0, window=0):
+                            guidance_rescale=0.0, flows=None, seed=None, unit=0, window=0, mask=None, source_latent=None, known_noise=None):
+        check_known_region(latent, mask, source_latent, known_noise)
         if flows is None:
             assert ref_images.shape[0] == 1, "only support batch size 1"
             flows = self.obtain_flow_batched(ref_images[0], query_images[0])
@@ -628,4 +683,5 @@ class InferenceIP2PVideoOpticalFlow(InferenceIP2PVideo):
         small = self._latent_flows(flows, latent.shape[1] - latent_ref.shape[1], h, w)
         return self._loop(latent, text_cond, text_uncond, img_cond, text_cfg, img_cfg, start_time, guidance_rescale,
                           latent_ref=latent_ref, noise_correct_step=noise_correct_step, flows=small,
-                          rng=_rng_of(dict(seed=seed, unit=unit, window=window)))
+                          rng=_rng_of(dict(seed=seed, unit=unit, window=window)),
+                          known=(mask, source_latent, known_noise) if mask is not None else None)

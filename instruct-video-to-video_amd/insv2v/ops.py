@@ -5,12 +5,13 @@ else.  No op has a torch/CPU fallback; non-CUDA tensors are rejected.
 """
 import ctypes as C
 
+import math
 import os
 import torch
 
 from . import _lib
 from .rng import as_int64
-from ._lib import GemmDesc, GroupNormDesc, LayerNormDesc, AttentionDesc, StepDesc, MStepDesc, FfnDesc, RowLinDesc, TattnDesc, XattnDesc, WinogradInDesc, WinogradOutDesc, check
+from ._lib import GemmDesc, GroupNormDesc, LayerNormDesc, AttentionDesc, StepDesc, MStepDesc, MaskStepDesc, FfnDesc, RowLinDesc, TattnDesc, XattnDesc, WinogradInDesc, WinogradOutDesc, check
 
 ACT_NONE, ACT_SILU, ACT_GEGLU, ACT_QUICK_GELU = 0, 1, 2, 3
 ACT_RELU, ACT_SIGMOID, ACT_TANH = 4, 5, 6   # the optical-flow network's (insv2v/raft.py)
@@ -719,15 +720,24 @@ def build_unet_input(latent, img_cond, out, t_out, timestep, nbranch, branch_row
 
 def cfg_step(eps_in, latent, *, nbranch, text_cfg=1.0, img_cfg=1.0, sqrt_a=1.0, sqrt_1ma=0.0, coef=(0, 0, 0, 0),
              latent_out=None, pred_x0=None, eps_out=None, latent_ref=None, correct=0, delta_q=None, noise=None,
-             rescale_stats=None, guidance_rescale=0.0, branch_stride=0, noise_seed=None, noise_stream=0, x0_hist=None, c_hist=0.0):
+             rescale_stats=None, guidance_rescale=0.0, branch_stride=0, noise_seed=None, noise_stream=0, x0_hist=None, c_hist=0.0,
+             mask=None, src=None, known_noise=None, k_src=0.0, k_noise=0.0):
     """``noise_seed`` / ``noise_stream``: the step's variance noise is generated inside the kernel from the seeded stream (element = flat
     index of [F,4,h,w]) instead of read from ``noise``; passing both is rejected by the kernel.
     ``x0_hist`` / ``c_hist``: the multistep term ``c_hist * x0_hist`` (the previous step's ``pred_x0``, DPM-Solver++ 2M).  Only a call
-    that gives a history goes to insv2v_cfg_step_ms (``cfg_step_ms``); every other call goes to insv2v_cfg_step as before."""
+    that gives a history goes to insv2v_cfg_step_ms (``cfg_step_ms``); every other call goes to insv2v_cfg_step as before.
+    ``mask`` [F,h,w] with ``src`` / ``known_noise`` [F,4,h,w] and ``k_src`` / ``k_noise``: behind the update, ``latent_out`` becomes
+    ``mask * prev + (1 - mask) * (k_src * src + k_noise * known_noise)`` (insv2v_cfg_step_mask, ``cfg_step_mask``).  Only a call that
+    gives a mask goes there."""
     kw = dict(nbranch=nbranch, text_cfg=text_cfg, img_cfg=img_cfg, sqrt_a=sqrt_a, sqrt_1ma=sqrt_1ma, coef=coef, latent_out=latent_out,
               pred_x0=pred_x0, eps_out=eps_out, latent_ref=latent_ref, correct=correct, delta_q=delta_q, noise=noise,
               rescale_stats=rescale_stats, guidance_rescale=guidance_rescale, branch_stride=branch_stride, noise_seed=noise_seed,
               noise_stream=noise_stream)
+    if mask is not None:
+        return cfg_step_mask(eps_in, latent, mask=mask, src=src, known_noise=known_noise, k_src=k_src, k_noise=k_noise, x0_hist=x0_hist,
+                             c_hist=c_hist, **kw)
+    if src is not None or known_noise is not None:
+        raise _lib.HipKernelError("cfg_step: src / known_noise need a mask")
     if x0_hist is not None:
         return cfg_step_ms(eps_in, latent, x0_hist=x0_hist, c_hist=c_hist, **kw)
     if c_hist != 0.0:
@@ -747,6 +757,73 @@ def cfg_step_ms(eps_in, latent, *, x0_hist=None, c_hist=0.0, **kw):
     d.x0_hist = _req(x0_hist, torch.float32, "x0_hist").data_ptr() if x0_hist is not None else None
     d.c_hist = c_hist
     check(lib.insv2v_cfg_step_ms(_byref(d), _stream()), "insv2v_cfg_step_ms")
+
+
+def cfg_step_mask(eps_in, latent, *, mask=None, src=None, known_noise=None, k_src=0.0, k_noise=0.0, x0_hist=None, c_hist=0.0, **kw):
+    """insv2v_cfg_step_mask: ``cfg_step_ms`` (its keywords) plus the blend of ``latent_out`` with the re-noised source latent outside
+    ``mask``.  ``mask`` fp32 [F,h,w] or None (then the result is bit-identical to ``cfg_step_ms`` / ``cfg_step``); ``src`` and
+    ``known_noise`` fp32 [F,4,h,w]; none of them may overlap an output."""
+    lib = _lib.load()
+    d = _fill_step_desc(MaskStepDesc(), eps_in, latent, **kw)
+    shape = tuple(latent.shape[-4:])
+    for name, t, want in (("x0_hist", x0_hist, shape), ("src", src, shape), ("known_noise", known_noise, shape),
+                          ("mask", mask, (shape[0],) + shape[2:])):
+        if t is None:
+            continue
+        _req(t, torch.float32, name)
+        if tuple(t.shape[-len(want):]) != want or t.numel() != math.prod(want) or not t.is_contiguous():
+            raise _lib.HipKernelError(f"cfg_step_mask: {name} {tuple(t.shape)} must be contiguous and shaped {want} (latent {tuple(latent.shape)})")
+    d.x0_hist, d.c_hist = _ptr(x0_hist), c_hist
+    d.mask, d.src, d.known_noise, d.k_src, d.k_noise = _ptr(mask), _ptr(src), _ptr(known_noise), k_src, k_noise
+    check(lib.insv2v_cfg_step_mask(_byref(d), _stream()), "insv2v_cfg_step_mask")
+
+
+def mask_to_latent(mask, mode="max"):
+    """Image-resolution mask fp32 [..., H, W] -> latent resolution [..., H/8, W/8]: per 8x8 cell its ``mode`` "mean" or "max"."""
+    if mode not in ("mean", "max"):
+        raise ValueError(f"mask_to_latent: mode {mode!r} is neither 'mean' nor 'max'")
+    lib = _lib.load()
+    _req(mask, torch.float32, "mask_to_latent.mask")
+    if mask.dim() < 2:
+        raise _lib.HipKernelError(f"mask_to_latent: mask {tuple(mask.shape)} needs [..., H, W]")
+    mask = mask.contiguous()
+    H, W = mask.shape[-2:]
+    N = mask.numel() // max(H * W, 1)
+    out = torch.empty((*mask.shape[:-2], H // 8, W // 8), device=mask.device, dtype=torch.float32)
+    check(lib.insv2v_mask_to_latent(mask.data_ptr(), out.data_ptr(), N, H, W, 1 if mode == "max" else 0, _stream()), "insv2v_mask_to_latent")
+    return out
+
+
+def composite(edited, original, mask, out=None):
+    """clip(mask * edited + (1 - mask) * original, -1, 1) on fp32 [N,3,H,W] frames with an image-resolution mask [N,H,W]; ``out`` may be
+    ``edited``."""
+    lib = _lib.load()
+    for name, t in (("edited", edited), ("original", original), ("mask", mask)):
+        _req(t, torch.float32, "composite." + name)
+        if not t.is_contiguous():
+            raise _lib.HipKernelError(f"composite: {name} must be contiguous")
+    if edited.dim() != 4 or edited.shape[1] != 3 or original.shape != edited.shape or tuple(mask.shape) != (edited.shape[0], *edited.shape[2:]):
+        raise _lib.HipKernelError(f"composite: edited {tuple(edited.shape)} / original {tuple(original.shape)} must be [N,3,H,W] and mask "
+                                  f"{tuple(mask.shape)} [N,H,W]")
+    if out is None:
+        out = torch.empty_like(edited)
+    elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.shape == edited.shape):
+        raise _lib.HipKernelError("composite: out must be a contiguous CUDA float32 tensor shaped like edited")
+    N, _, H, W = edited.shape
+    check(lib.insv2v_composite(edited.data_ptr(), original.data_ptr(), mask.data_ptr(), out.data_ptr(), N, H, W, _stream()), "insv2v_composite")
+    return out
+
+
+def add_noise(z, noise, ka, kb):
+    """ka * z + kb * noise (fp32, any shape): the source latent re-noised to the level (ka, kb) = (sqrt(a), sqrt(1 - a))."""
+    lib = _lib.load()
+    _req(z, torch.float32, "add_noise.z"), _req(noise, torch.float32, "add_noise.noise")
+    if z.shape != noise.shape:
+        raise _lib.HipKernelError(f"add_noise: z {tuple(z.shape)} and noise {tuple(noise.shape)} differ")
+    z, noise = z.contiguous(), noise.contiguous()
+    out = torch.empty_like(z)
+    check(lib.insv2v_add_noise(z.data_ptr(), noise.data_ptr(), out.data_ptr(), z.numel(), ka, kb, _stream()), "insv2v_add_noise")
+    return out
 
 
 def _fill_step_desc(d, eps_in, latent, *, nbranch, text_cfg=1.0, img_cfg=1.0, sqrt_a=1.0, sqrt_1ma=0.0, coef=(0, 0, 0, 0),

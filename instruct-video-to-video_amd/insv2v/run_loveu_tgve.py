@@ -17,6 +17,7 @@ import torch
 
 from . import ops
 from .rng import stream_id, INIT
+from .schedulers import strength_to_start
 
 
 def split_batch(cond, frames_in_batch=16, num_ref_frames=4):
@@ -41,10 +42,82 @@ def _seeded(seed, unit):
     return {} if seed is None else {"seed": seed, "unit": unit}
 
 
+MASK_MODES = ("mean", "max")
+
+
+def check_edit_args(frames_shape, mask=None, strength=1.0, mask_mode="max"):
+    """Host-side check of the localized / partial edit controls (nothing is launched): ``strength`` in (0, 1], ``mask_mode`` "mean" or
+    "max", ``mask`` a floating-point [1,T,H,W] or [1,1,H,W] tensor for frames [1,T,3,H,W] with H and W multiples of 8."""
+    strength_to_start(strength, 1)
+    if mask_mode not in MASK_MODES:
+        raise ValueError(f"mask_mode {mask_mode!r} is neither 'mean' nor 'max'")
+    if mask is None:
+        return
+    b, T, _, H, W = frames_shape
+    if not torch.is_tensor(mask) or not mask.is_floating_point():
+        raise ValueError("mask must be a floating-point tensor with values in [0, 1] (1 = edit, 0 = keep)")
+    if mask.dim() != 4 or mask.shape[0] != 1 or b != 1 or mask.shape[1] not in (1, T) or tuple(mask.shape[2:]) != (H, W):
+        raise ValueError(f"mask {tuple(mask.shape)} must be [1,{T},{H},{W}] or [1,1,{H},{W}] (image resolution) for frames {tuple(frames_shape)}")
+    if H % 8 or W % 8:
+        raise ValueError(f"a mask needs frame sizes that are multiples of 8 (one latent cell per 8x8 pixels), not {H}x{W}")
+
+
+def _start_time(inf_pipe, strength):
+    """``start_time`` of an edit of this strength (full strength asks the pipe nothing: any pipe object keeps working)."""
+    return 0 if strength == 1.0 else strength_to_start(strength, inf_pipe.num_ddim_steps)[1]
+
+
+class _EditPlan:
+    """What a localized (``mask``) or partial (``strength`` < 1) edit adds to the windows of one unit: the source latent z and the
+    latent-resolution mask, split like ``cond``, and the level the trajectory starts from.  ``active`` is False for a plain edit, whose
+    calls then carry no new keyword."""
+
+    def __init__(self, model, inf_pipe, frames, cond, mask, strength, mask_mode, frames_in_batch, num_ref_frames, z=None):
+        dev = model.unet.device
+        self.start_time = _start_time(inf_pipe, strength)
+        partial = strength != 1.0   # (also a strength below 1 that rounds to every step: it starts from the noised source at timesteps[0])
+        self.active = mask is not None or partial
+        self.mask_img = self.masks = self.level = None
+        if not self.active:
+            return
+        if z is None:   # (a caller's ``cond`` is z / scale_factor)
+            z = cond * model.scale_factor
+        self.zs = split_batch(z.to(device=dev, dtype=torch.float32), frames_in_batch, num_ref_frames)[0]
+        if partial:
+            self.level = inf_pipe.scheduler.start_coefficients(int(inf_pipe.scheduler.timesteps[self.start_time]))
+        if mask is not None:
+            T = frames.shape[1]
+            self.mask_img = mask.to(device=dev, dtype=torch.float32).expand(1, T, *mask.shape[2:])[0].contiguous()   # [T,H,W]
+            self.masks = split_batch(ops.mask_to_latent(self.mask_img, mask_mode)[None], frames_in_batch, num_ref_frames)[0]   # reduced ONCE
+
+    def window(self, k, R, init):
+        """(initial latent, extra keywords) of window k, whose first R frames are carried over; ``init`` = the window's initial noise."""
+        if not self.active:
+            return init, {}
+        join = (lambda c: c[0]) if k == 0 else (lambda c: torch.cat([c[k - 1][:, -R:], c[k]], dim=1))   # exactly as cond_k
+        z = join(self.zs)
+        kw = {}
+        latent = init
+        if self.level is not None:
+            latent = ops.add_noise(z, init, *self.level)
+            kw["start_time"] = self.start_time
+        if self.masks is not None:
+            kw.update(mask=join(self.masks).contiguous(), source_latent=z, known_noise=init)
+        return latent, kw
+
+    def finish(self, image, frames):
+        """Decoded frames [1,T,3,H,W] -> the result: composited against the input outside the mask, clipped to [-1,1]."""
+        if self.mask_img is None:
+            return image.clip(-1, 1)
+        img = image[0].to(torch.float32).contiguous()
+        orig = frames[0].to(device=img.device, dtype=torch.float32).contiguous()
+        return ops.composite(img, orig, self.mask_img, out=img)[None]
+
+
 @torch.no_grad()
 def edit_video(model, inf_pipe, frames, text_cond, text_uncond, text_cfg=7.5, video_cfg=1.8, frames_in_batch=16,
                num_ref_frames=4, init_noises=None, enc_noise=None, flows_per_window=None, return_latent=False, cond=None,
-               seed=None, unit=0):
+               seed=None, unit=0, mask=None, strength=1.0, mask_mode="max"):
     """frames [1,T,3,H,W] in [-1,1] -> edited frames [1,T,3,H,W] clipped to [-1,1].
 
     ``seed`` (default None: every draw comes from the global torch generators, as before) makes the edit reproducible: the posterior
@@ -58,11 +131,22 @@ def edit_video(model, inf_pipe, frames, text_cond, text_uncond, text_cfg=7.5, vi
     flows; without it an optical-flow pipe gets the frames of the previous / current window (``ref_images`` /
     ``query_images``, insv2v_run_loveu_tgve.py:141-160) and runs its injected ``flow_estimator``.
     ``cond`` = an already encoded conditioning latent: the reference encodes a video ONCE and shares the posterior
-    sample across its four prompts (:98)."""
+    sample across its four prompts (:98).
+
+    ``mask`` ([1,T,H,W] at image resolution, or [1,1,H,W] for all frames; 1 = edit, 0 = keep; soft values allowed) makes the edit
+    local: it is reduced to latent resolution once (``mask_mode`` "max" - a cell is edited if any of its 8x8 pixels is - or "mean"),
+    every step holds the latent outside it at the source video's, re-noised to that step's level with the window's initial noise
+    (inside the step kernel), and the result is composited against the input frames, so pixels outside the mask ARE the input's.
+    ``strength`` in (0, 1] makes the edit partial: only the last ``round(strength * steps)`` steps run, and at every strength below
+    1.0 - also one that rounds to all steps - from the source latent noised to the first executed step's level instead of from pure noise.  With ``mask=None, strength=1.0`` the calls are exactly what they were."""
+    check_edit_args(frames.shape, mask, strength, mask_mode)
     dev = model.unet.device
+    z = None
     if cond is None:
-        cond = model.encode_image_to_latent(frames, enc_noise, **_seeded(seed, unit)) / model.scale_factor
+        z = model.encode_image_to_latent(frames, enc_noise, **_seeded(seed, unit))
+        cond = z / model.scale_factor
     conds, refs = split_batch(cond, frames_in_batch, num_ref_frames)
+    plan = _EditPlan(model, inf_pipe, frames, cond, mask, strength, mask_mode, frames_in_batch, num_ref_frames, z=z)
     frame_chunks, _ = split_batch(frames, frames_in_batch, num_ref_frames)
     rng = _seeded(seed, unit)
     wants_flow = hasattr(inf_pipe, "obtain_flow_batched")
@@ -77,8 +161,9 @@ def edit_video(model, inf_pipe, frames, text_cond, text_uncond, text_cfg=7.5, vi
         return torch.randn(like.shape, device=dev, dtype=torch.float32)
 
     init = draw(0, conds[0])
-    pred = inf_pipe(latent=init, text_cond=text_cond, text_uncond=text_uncond, img_cond=conds[0],
-                    text_cfg=text_cfg, img_cfg=video_cfg, **rng)["latent"]
+    start, known = plan.window(0, 0, init)
+    pred = inf_pipe(latent=start, text_cond=text_cond, text_uncond=text_uncond, img_cond=conds[0],
+                    text_cfg=text_cfg, img_cfg=video_cfg, **rng, **known)["latent"]
     preds = [pred]
     for k, (prev_cond, cond_k, R) in enumerate(zip(conds[:-1], conds[1:], refs)):
         init = torch.cat([init[:, -R:], draw(k + 1, cond_k)], dim=1)  # overlap re-uses the INITIAL noise (:139)
@@ -89,12 +174,14 @@ def edit_video(model, inf_pipe, frames, text_cond, text_uncond, text_cfg=7.5, vi
         elif wants_flow:
             prev_frames = torch.cat(frame_chunks[:k + 1], dim=1)
             kw["ref_images"], kw["query_images"] = prev_frames[:, -R:], frame_chunks[k + 1]
-        pred = inf_pipe.second_clip_forward(latent=init, text_cond=text_cond, text_uncond=text_uncond, img_cond=cond_k,
+        start, known = plan.window(k + 1, R, init)
+        kw.update(known)
+        pred = inf_pipe.second_clip_forward(latent=start, text_cond=text_cond, text_uncond=text_uncond, img_cond=cond_k,
                                             latent_ref=pred[:, -R:], noise_correct_step=0.5, text_cfg=text_cfg,
                                             img_cfg=video_cfg, **kw)["latent"]
         preds.append(pred[:, R:])
     latent = torch.cat(preds, dim=1)
-    image = model.decode_latent_to_image(latent).clip(-1, 1)
+    image = plan.finish(model.decode_latent_to_image(latent), frames)
     return (image, latent) if return_latent else image
 
 
@@ -111,13 +198,20 @@ def edit_videos(model, inf_pipe, units, frames_in_batch=16, num_ref_frames=4, re
     elementwise work behind the shared UNet launch, so optical-flow units stack like the others (round 5).
     ``seed``: as for ``edit_video``; a unit's id is ``u.get("unit", position in the list)``, so a unit that carries its id gets the same
     noise in any list, at any position.
-    ``max_clips``: units per launch chain, as for ``run_stacked`` (None: its default cap, ``max_clips_in_flight``)."""
+    ``max_clips``: units per launch chain, as for ``run_stacked`` (None: its default cap, ``max_clips_in_flight``).
+    A unit may carry ``mask``, ``strength`` and ``mask_mode`` as for ``edit_video``: masked and unmasked units stack together; the units
+    of one call must share the number of executed steps (a stack shares ``start_time``), so strengths that round to different step
+    counts raise ValueError."""
     if len(units) == 0:
         return []
+    for u in units:
+        check_edit_args(u["frames"].shape, u.get("mask"), u.get("strength", 1.0), u.get("mask_mode", "max"))
+    if len({_start_time(inf_pipe, u.get("strength", 1.0)) for u in units}) > 1:
+        raise ValueError("edit_videos: the units of one call must share the number of executed steps (strength); edit the others separately")
     wants_flow = hasattr(inf_pipe, "obtain_flow_batched")
     ids = [u.get("unit", j) for j, u in enumerate(units)]
     if len(units) == 1:
-        keys = ("text_cfg", "video_cfg", "init_noises", "enc_noise", "cond", "flows_per_window")
+        keys = ("text_cfg", "video_cfg", "init_noises", "enc_noise", "cond", "flows_per_window", "mask", "strength", "mask_mode")
         return [edit_video(model, inf_pipe, u["frames"], u["text_cond"], u["text_uncond"], frames_in_batch=frames_in_batch,
                            num_ref_frames=num_ref_frames, return_latent=return_latent, seed=seed, unit=ids[0],
                            **{k: u[k] for k in keys if k in u}) for u in units]
@@ -128,13 +222,16 @@ def edit_videos(model, inf_pipe, units, frames_in_batch=16, num_ref_frames=4, re
     for u, uid in zip(units, ids):
         if tuple(u["frames"].shape) != shape:
             raise ValueError("edit_videos: all units must share [1,T,3,H,W]")
-        cond = u.get("cond")
+        cond, z = u.get("cond"), None
         if cond is None:
-            cond = model.encode_image_to_latent(u["frames"], u.get("enc_noise"), **_seeded(seed, uid)) / model.scale_factor
+            z = model.encode_image_to_latent(u["frames"], u.get("enc_noise"), **_seeded(seed, uid))
+            cond = z / model.scale_factor
         conds, refs = split_batch(cond, frames_in_batch, num_ref_frames)
+        plan = _EditPlan(model, inf_pipe, u["frames"], cond, u.get("mask"), u.get("strength", 1.0), u.get("mask_mode", "max"),
+                         frames_in_batch, num_ref_frames, z=z)
         if wants_flow and u.get("flows_per_window") is None and getattr(inf_pipe, "flow_estimator", None) is None and len(conds) > 1:
             raise RuntimeError("optical-flow pipeline without a flow source: pass flows_per_window= or build the pipe with flow_estimator=")
-        st.append(dict(u=u, unit=uid, conds=conds, refs=refs, preds=[], init=None, pred=None,
+        st.append(dict(u=u, unit=uid, conds=conds, refs=refs, preds=[], init=None, pred=None, plan=plan,
                        frame_chunks=split_batch(u["frames"], frames_in_batch, num_ref_frames)[0] if wants_flow else None))
 
     def draw(s, k, like):
@@ -155,7 +252,8 @@ def edit_videos(model, inf_pipe, units, frames_in_batch=16, num_ref_frames=4, re
     calls = []
     for s in st:
         s["init"] = draw(s, 0, s["conds"][0])
-        calls.append(dict(common(s, 0), latent=s["init"], img_cond=s["conds"][0]))
+        start, known = s["plan"].window(0, 0, s["init"])
+        calls.append(dict(common(s, 0), latent=start, img_cond=s["conds"][0], **known))
     for s, r in zip(st, inf_pipe.run_stacked(calls, **cap)):
         s["pred"] = r["latent"]
         s["preds"].append(s["pred"])
@@ -164,7 +262,8 @@ def edit_videos(model, inf_pipe, units, frames_in_batch=16, num_ref_frames=4, re
         for s in st:
             s["init"] = torch.cat([s["init"][:, -R:], draw(s, k + 1, s["conds"][k + 1])], dim=1)  # overlap re-uses the INITIAL noise (:139)
             cond_k = torch.cat([s["conds"][k][:, -R:], s["conds"][k + 1]], dim=1)
-            call = dict(common(s, k + 1), latent=s["init"], img_cond=cond_k, latent_ref=s["pred"][:, -R:], noise_correct_step=0.5)
+            start, known = s["plan"].window(k + 1, R, s["init"])
+            call = dict(common(s, k + 1), latent=start, img_cond=cond_k, latent_ref=s["pred"][:, -R:], noise_correct_step=0.5, **known)
             if s["u"].get("flows_per_window") is not None:
                 call["flows"] = s["u"]["flows_per_window"][k]
             elif wants_flow:   # ref_images = the last R frames before this window, query_images = its new frames (:141-147)
@@ -177,7 +276,7 @@ def edit_videos(model, inf_pipe, units, frames_in_batch=16, num_ref_frames=4, re
     outs = []
     for s in st:
         latent = torch.cat(s["preds"], dim=1)
-        image = model.decode_latent_to_image(latent).clip(-1, 1)
+        image = s["plan"].finish(model.decode_latent_to_image(latent), s["u"]["frames"])
         outs.append((image, latent) if return_latent else image)
     return outs
 
@@ -211,6 +310,12 @@ def build_parser():
     p.add_argument("--max-stack", type=int, default=None,
                    help="units per stacked launch chain (default: inference.max_clips_in_flight of the clip shape, at most 20); any stack "
                         "that fits in memory runs, a frame that no kernel can address is refused before the first launch")
+    p.add_argument("--strength", type=float, default=1.0,
+                   help="partial edit: in (0, 1]; only the last round(strength * steps) steps run, from the noised source latent (1.0: from pure noise)")
+    p.add_argument("--mask-mode", type=str, default="max",
+                   help="mean | max: how an image-resolution mask (the optional \"mask\" entry of a --units file, [n,T,H,W] or [n,1,H,W]; "
+                        "--synthetic-mask) is reduced to one value per 8x8 latent cell")
+    p.add_argument("--synthetic-mask", action="store_true", help="with --synthetic: edit only a centred rectangle (half the height and width) of every frame")
     p.add_argument("--raft-ckpt", type=str, default=None,
                    help="torchvision raft_large checkpoint (state dict) for --with_optical_flow: the estimator runs on the HIP kernels")
     p.add_argument("--flows", type=str, default=None,
@@ -227,9 +332,23 @@ def check_args(args):
         raise SystemExit("--with_optical_flow needs --raft-ckpt FILE (torchvision raft_large weights) or --flows FILE (precomputed flows)")
     if getattr(args, "max_stack", None) is not None and args.max_stack < 1:
         raise SystemExit("--max-stack needs a positive number of units")
+    strength = getattr(args, "strength", 1.0)
+    if not (0.0 < strength <= 1.0):
+        raise SystemExit(f"--strength must be in (0, 1], not {strength}")
+    if getattr(args, "mask_mode", "max") not in MASK_MODES:
+        raise SystemExit(f"--mask-mode must be mean or max, not {args.mask_mode}")
+    if getattr(args, "synthetic_mask", False) and not args.synthetic:
+        raise SystemExit("--synthetic-mask needs --synthetic N (masks of real units come from the \"mask\" entry of a --units file)")
     if args.flows and args.units is None and not args.synthetic:
         raise SystemExit("--flows is supported with --units / --synthetic (flows are indexed by unit)")
     return args
+
+
+def synthetic_mask(n, H, W):
+    """[n,1,H,W]: 1 inside the centred rectangle of half the height and width, 0 outside (--synthetic-mask)."""
+    m = torch.zeros((n, 1, H, W), dtype=torch.float32)
+    m[:, :, H // 4:H - H // 4, W // 4:W - W // 4] = 1.0
+    return m
 
 
 def optical_flow_pipe_kwargs(args):
@@ -273,7 +392,8 @@ def run_dataset(args, model, pipe, rank=0, world=1):
                 print(f"File {gif_path} exists, skip")
                 continue
             todo.append((gif_path, image_dir, dict(frames=frames, text_cond=model.encode_text([prompt]), text_uncond=text_uncond,
-                                                   text_cfg=text_cfg, video_cfg=video_cfg, cond=cond, unit=4 * ci + kinds.index(key))))
+                                                   text_cfg=text_cfg, video_cfg=video_cfg, cond=cond, unit=4 * ci + kinds.index(key),
+                                                   strength=getattr(args, "strength", 1.0))))
         # the four prompts of a video share the conditioning latent and the window plan: one stacked launch chain per window (B = 12)
         if getattr(args, "no_stack", False):
             edits = [edit_videos(model, pipe, [u], seed=seed)[0] for _, _, u in todo]
@@ -317,6 +437,8 @@ def main(argv=None):
         data = {"frames": torch.rand((args.synthetic, T, 3, S, S), generator=g) * 2 - 1,
                 "text_cond": torch.randn((args.synthetic, 77, 768), generator=g),
                 "text_uncond": torch.randn((1, 77, 768), generator=g)}
+        if args.synthetic_mask:
+            data["mask"] = synthetic_mask(args.synthetic, S, S)
     elif args.units is None:
         cls = InferenceIP2PVideoOpticalFlow if args.with_optical_flow else InferenceIP2PVideo
         run_dataset(args, model, cls(unet=model.unet, num_ddim_steps=args.steps, scheduler=args.scheduler, solver_order=args.solver_order, **optical_flow_pipe_kwargs(args)), rank, world)
@@ -330,6 +452,8 @@ def main(argv=None):
     n = data["frames"].shape[0]
     flows = torch.load(args.flows, map_location="cpu") if args.flows else None
     item_shape = tuple(data["frames"].shape[1:])  # a rank without units still takes part in the all_gather
+    masks = data.get("mask")   # optional [n,T,H,W] / [n,1,H,W]
+    edit = lambda i: dict(mask=masks[i:i + 1] if masks is not None else None, strength=args.strength, mask_mode=args.mask_mode)
     outs = []
     for ci, (text_cfg, video_cfg) in enumerate(product(args.text_cfg, args.video_cfg)):
         mine = shard_units(n, rank, world)
@@ -338,7 +462,7 @@ def main(argv=None):
         if args.no_stack:
             local_out = [edit_video(model, pipe, data["frames"][i:i + 1], data["text_cond"][i:i + 1], data["text_uncond"],
                                     text_cfg, video_cfg, flows_per_window=flows[i] if flows is not None else None,
-                                    seed=args.seed, unit=ci * n + i) for i in mine]
+                                    seed=args.seed, unit=ci * n + i, **edit(i)) for i in mine]
         else:   # a rank's units as stacked launch chains (run_stacked caps the stack at what the kernels' operand window allows)
             from .inference import max_clips_in_flight
             T, S = data["frames"].shape[1], data["frames"].shape[-1]
@@ -346,7 +470,7 @@ def main(argv=None):
             local_out = []
             for g in range(0, len(mine), cap):
                 local_out += edit_videos(model, pipe, [dict(frames=data["frames"][i:i + 1], text_cond=data["text_cond"][i:i + 1],
-                                                            text_uncond=data["text_uncond"], text_cfg=text_cfg, video_cfg=video_cfg, unit=ci * n + i,
+                                                            text_uncond=data["text_uncond"], text_cfg=text_cfg, video_cfg=video_cfg, unit=ci * n + i, **edit(i),
                                                             **({"flows_per_window": flows[i]} if flows is not None else {}))
                                                        for i in mine[g:g + cap]], seed=args.seed, max_clips=args.max_stack)
         local_out = torch.cat(local_out, 0).half() if local_out else torch.zeros((0, *item_shape), device=model.unet.device).half()

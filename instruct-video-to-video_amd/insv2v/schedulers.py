@@ -9,6 +9,8 @@ diffusers); the tensor update runs in insv2v_cfg_step:
 
 DPMSolverMultistepScheduler (DPM-Solver++ 2M, Lu et al. 2022, data-prediction form; ODE and SDE) adds one term, c_hist times the x0
 prediction of the previous executed step (insv2v_cfg_step_ms).
+
+``strength_to_start`` maps an edit strength in (0, 1] to the number of executed steps / ``start_time`` of a partial edit.
 """
 import math
 
@@ -25,6 +27,23 @@ class _Schedule:
         self.alphas_cumprod = torch.cumprod(1.0 - self.betas, dim=0)
         self.num_inference_steps = None
         self.timesteps = None
+
+    def _end_alpha(self):
+        """The cumulative alpha a step lands at once prev < 0 (each scheduler's own end point)."""
+        return self.final_alpha_cumprod
+
+    def known_coefficients(self, t):
+        """-> (k_src, k_noise) = (sqrt(a_prev), sqrt(1 - a_prev)), a_prev the cumulative alpha the output of step ``t`` lives at: what a
+        masked step re-noises the source latent with (``known = k_src * z + k_noise * n``, DESIGN.md "Masked and partial edits").
+        Computed in float64, handed over as fp32-valued python floats."""
+        prev = int(t) - self.num_train_timesteps // self.num_inference_steps
+        a_prev = float(self.alphas_cumprod[prev].double()) if prev >= 0 else float(torch.as_tensor(self._end_alpha()).double())
+        return float(np.float32(math.sqrt(a_prev))), float(np.float32(math.sqrt(1.0 - a_prev)))
+
+    def start_coefficients(self, t):
+        """-> (sqrt(a_t), sqrt(1 - a_t)) as fp32-valued floats: the level a partial edit (strength < 1) starts from at timestep ``t``."""
+        a_t = float(self.alphas_cumprod[int(t)].double())
+        return float(np.float32(math.sqrt(a_t))), float(np.float32(math.sqrt(1.0 - a_t)))
 
     def _leading(self, n, offset):
         ratio = self.num_train_timesteps // n
@@ -65,6 +84,9 @@ class DDPMScheduler(_Schedule):
     def set_timesteps(self, n):
         self.num_inference_steps = n
         self.timesteps = self._leading(n, 0)
+
+    def _end_alpha(self):
+        return 1.0
 
     def coefficients(self, t):
         prev = t - self.num_train_timesteps // self.num_inference_steps
@@ -144,3 +166,13 @@ class DPMSolverMultistepScheduler(_Schedule):
         f32 = lambda v: float(np.float32(v))
         return dict(sqrt_a=float(a_t ** 0.5), sqrt_1ma=float((1 - a_t) ** 0.5), coef=(f32(c_x0), 0.0, f32(c_xt), f32(c_noise)),
                     c_hist=f32(c_hist) if second else 0.0)
+
+
+def strength_to_start(strength, steps):
+    """Edit strength s in (0, 1] -> (n_exec, start_time): n_exec = min(steps, max(1, floor(s * steps + 0.5))) steps are executed, from
+    ``timesteps[start_time]`` = ``timesteps[steps - n_exec]`` on.  s == 1.0 is the full trajectory from pure noise."""
+    s = float(strength)
+    if not (0.0 < s <= 1.0):   # (also refuses NaN)
+        raise ValueError(f"strength must be in (0, 1], not {strength!r}")
+    n_exec = min(int(steps), max(1, int(math.floor(s * steps + 0.5))))
+    return n_exec, int(steps) - n_exec
