@@ -414,7 +414,11 @@ int insv2v_layernorm_stats(const void* x, float* stats, int64_t ldx, int32_t row
  *     seq_k = 77;
  *   - temporal self-attention over frames (motion_module.py:270-336, F.scaled_dot_product_attention
  *     in the reference): z = (b, pixel), rows = frames, row stride = h*w*ld.
- * head_dim must be a multiple of 8 and <= 160; seq_k >= 1.
+ * head_dim is one of 16, 32, 40, 64, 80, 128, 160 or 512 (INSV2V_EUNSUPPORTED for another multiple of 8 up to 160, INSV2V_EINVAL for
+ * anything else); seq_q, seq_k >= 1.
+ * head_dim = 512 (the VAE's one-head mid AttnBlock, modules/vqvae/model.py:145-197): plain softmax only - causal != 0 or bias tables
+ * return INSV2V_EUNSUPPORTED; any seq_q / seq_k / batch / heads; one problem's K and V rows have to lie within 2 GiB of its base
+ * (seq_k * max(k_rs, v_rs) * 2 bytes; INSV2V_EUNSUPPORTED beyond), the per-problem bases themselves are 64-bit.
  */
 typedef struct insv2v_attention_desc {
     const void* q;

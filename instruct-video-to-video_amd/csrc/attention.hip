@@ -767,7 +767,7 @@ extern "C" int insv2v_attention(const insv2v_attention_desc* dp, insv2v_stream_t
     if (!dp) return INSV2V_EINVAL;
     insv2v_attention_desc d = *dp;
     if (!d.q || !d.k || !d.v || !d.o) return INSV2V_EINVAL;
-    if (d.head_dim <= 0 || (d.head_dim & 7) || d.head_dim > 160) return INSV2V_EINVAL;
+    if (d.head_dim <= 0 || (d.head_dim & 7) || (d.head_dim > 160 && d.head_dim != 512)) return INSV2V_EINVAL;
     if (d.seq_q <= 0 || d.seq_k <= 0 || d.batch <= 0 || d.heads <= 0) return INSV2V_EINVAL;
     if ((d.q_rs & 7) || (d.k_rs & 7) || (d.v_rs & 7) || (d.o_rs & 3)) return INSV2V_EINVAL;
     if (d.q_inner <= 0) d.q_inner = 1;
@@ -779,6 +779,14 @@ extern "C" int insv2v_attention(const insv2v_attention_desc* dp, insv2v_stream_t
     const bool biased = d.q_bias || d.k_bias || d.v_bias;
     if (biased && (!d.q_bias || !d.k_bias || !d.v_bias || (d.bias_rs & 7) || ((uintptr_t)d.q_bias & 15) || ((uintptr_t)d.k_bias & 15) || ((uintptr_t)d.v_bias & 15)))
         return INSV2V_EINVAL;
+    // d = 512 (the VAE's one-head mid block): one form for every sequence length - four waves x 16 query rows over double-buffered 32-key
+    // tiles (137 KiB of LDS, one workgroup per CU, one wave per SIMD with O^T in 128 accumulator registers).  Plain softmax only.
+    if (d.head_dim == 512) {
+        if (d.causal || biased) return INSV2V_EUNSUPPORTED;
+        // the K / V tile loads are 32-bit byte offsets from the (problem, head) base
+        if (((int64_t)d.seq_k * std::max(d.k_rs, d.v_rs) + 512) * 2 > 0x7fffffffLL) return INSV2V_EUNSUPPORTED;
+        return launch_attn<512, 4, 1, false, 32>(d, s);
+    }
     if ((short_on || biased) && d.seq_q <= 16 && d.seq_k <= 16 && !d.causal && d.heads <= 16) {
         const int rc = dispatch_short(d, s);
         if (rc != INSV2V_EUNSUPPORTED || biased) return rc;

@@ -4,17 +4,48 @@ keys (encoder.*, decoder.*, quant_conv.*, post_quant_conv.*).
 
 Channels-last fp16 throughout; frames are batched (the reference decodes one frame at a time,
 instruct_p2p_video.py:73-76 -- same values, fewer launches).  The mid AttnBlock (model.py:145-197,
-single head, C=512) is three batched GEMMs + a row softmax: S = q k^T / sqrt(C), P = softmax(S),
-O = P v, with v^T produced directly by a GEMM so no transpose kernel is needed.
+single head, C=512) has two forms, chosen by ``attn_plan``:
+  "scores"  three batched GEMMs + a row softmax: S = q k^T / sqrt(C), P = softmax(S), O = P v, with v^T
+            produced directly by a GEMM so no transpose kernel is needed.  The [N, h*w, h*w] scores live in
+            memory: every geometry up to h*w = 4096 (all that is benched or pinned by a golden) runs this form;
+  "flash"   q | k | v row GEMMs into one [N*h*w, 3C] matrix + insv2v_attention (one head of C channels, online
+            softmax): nothing of size (h*w)^2 exists, so a frame of any size runs.  C = 128 and 512 only.
 """
 import torch
 
 from . import ops
+from .fused import OPERAND_WINDOW
 from .rng import stream_id, ENC
 from .unet import prep_conv3x3, prep_linear, prep_norm, _dev
 
 EPS = 1e-6
 GROUPS = 32
+# The score tensor of one chunk of frames passes half a GB from here on (15 frames x 4096^2 x 2 B at 512 x 512): a memory rule, not a
+# measured crossover.  Every geometry with a golden or a bench number lies below it and launches what it always launched.
+FLASH_MIN_HW = 4096
+FLASH_WIDTHS = (128, 512)   # head dims insv2v_attention dispatches that a VAE mid block can have (VAE_TINY, full width)
+# insv2v_gemm refuses a BATCHED problem with an operand beyond one window (gemm.hip beyond_window(); its default window keeps 1 MiB
+# of headroom below 2 GiB): the score matrix of ONE frame, HW x HWp fp16, has to stay below this
+SCORE_WINDOW = OPERAND_WINDOW - 2 ** 20
+
+
+def attn_plan(C, HW, flash=None):
+    """Which form the mid AttnBlock of C channels takes at h*w = HW tokens: "scores" or "flash".  flash=None: the memory rule above;
+    True / False force a form.  Raises ValueError, before anything is launched, for a form that cannot run.  Pure arithmetic."""
+    C, HW = int(C), int(HW)
+    if flash is None:
+        flash = C in FLASH_WIDTHS and HW > FLASH_MIN_HW
+    if flash:
+        if C not in FLASH_WIDTHS:
+            raise ValueError(f"VAE attention of C = {C} channels at h*w = {HW}: the flash form takes C in {FLASH_WIDTHS} only "
+                             f"(the score form would hold {HW * ((HW + 7) // 8 * 8) * 2} bytes of scores per frame)")
+        return "flash"
+    HWp = (HW + 7) // 8 * 8
+    if HW * HWp * 2 >= SCORE_WINDOW:
+        raise ValueError(f"VAE attention of C = {C} channels at h*w = {HW}: one frame's score matrix is {HW * HWp * 2} bytes, and the batched "
+                         f"score GEMM addresses it through one window of {SCORE_WINDOW} bytes"
+                         + ("" if C in FLASH_WIDTHS else f"; the flash form takes C in {FLASH_WIDTHS} only"))
+    return "scores"
 
 
 class VResBlock:
@@ -34,8 +65,9 @@ class VResBlock:
 
 
 class VAttn:
-    def __init__(self, sd, key, ch, dev):
+    def __init__(self, sd, key, ch, dev, flash=None):
         self.ch = ch
+        self.flash = flash   # None: attn_plan's memory rule; True / False: force the form
         self.norm = prep_norm(sd, key + ".norm", dev)
         self.wqk = _dev(torch.cat([sd[f"{key}.{n}.weight"].reshape(ch, ch).float() for n in "qk"], 0), torch.float16, dev)
         self.bqk = _dev(torch.cat([sd[f"{key}.{n}.bias"].float() for n in "qk"], 0), torch.float32, dev)
@@ -45,6 +77,8 @@ class VAttn:
     def __call__(self, x, geom):
         N, H, W = geom
         C, HW = self.ch, H * W
+        if attn_plan(C, HW, self.flash) == "flash":
+            return self._flash(x, N, HW)
         # The batched GEMMs want 16-byte leading dimensions (ldc = HW of the scores, K = HW of P.v): for an h*w that is not a multiple of 8
         # the score rows and v^T rows are padded to HWp columns.  The softmax writes the pad columns of P as exact zeros and v^T's pad
         # columns are zero, so contracting over HWp adds nothing.  HW % 8 == 0: HWp = HW, the launches of before.
@@ -64,10 +98,27 @@ class VAttn:
                  ldc=C, a_bs=HW * HWp, w_bs=C * HWp, c_bs=HW * C)
         return ops.gemm(o, *self.proj, residual=x)
 
+    def _flash(self, x, N, HW):
+        """q | k and v (bias in its GEMM) as column ranges of one [N*HW, 3C] matrix, so that one problem stride serves all three operands of
+        insv2v_attention; one head of C channels per frame."""
+        C = self.ch
+        n = ops.groupnorm(x, N, HW, *self.norm, GROUPS, EPS)
+        qkv = torch.empty((N * HW, 3 * C), device=x.device, dtype=torch.float16)
+        ops.gemm(n, self.wqk, self.bqk, out=qkv[:, :2 * C])
+        ops.gemm(n, self.wv, self.bv, out=qkv[:, 2 * C:])
+        del n
+        o = torch.empty((N * HW, C), device=x.device, dtype=torch.float16)
+        p = qkv.data_ptr()
+        ops.attention(p, p + 2 * C, p + 4 * C, o, batch=N, heads=1, head_dim=C, seq_q=HW, seq_k=HW, scale=float(C) ** -0.5,
+                      q_rs=3 * C, k_rs=3 * C, v_rs=3 * C, o_rs=C, q_addr=(1, HW * 3 * C, 0), kv_addr=(1, HW * 3 * C, 0), o_addr=(1, HW * C, 0))
+        del qkv
+        return ops.gemm(o, *self.proj, residual=x)
+
 
 class AutoencoderKL:
-    def __init__(self, ddconfig, embed_dim=4, device="cuda", **unused):
+    def __init__(self, ddconfig, embed_dim=4, device="cuda", attn_flash=None, **unused):
         self.dd = dict(ddconfig)
+        self.attn_flash = attn_flash   # the mid AttnBlocks' form: None = attn_plan's rule, True / False force it
         self.embed_dim = embed_dim
         self.device = torch.device(device)
         if len(self.dd.get("attn_resolutions", [])):
@@ -92,7 +143,7 @@ class AutoencoderKL:
                 cur = ch * mult[lvl]
             ds = prep_conv3x3(sd, f"{e}.down.{lvl}.downsample.conv", dev) if lvl != len(mult) - 1 else None
             self.e_down.append((blocks, ds))
-        self.e_mid = (VResBlock(sd, e + ".mid.block_1", cur, cur, dev), VAttn(sd, e + ".mid.attn_1", cur, dev),
+        self.e_mid = (VResBlock(sd, e + ".mid.block_1", cur, cur, dev), VAttn(sd, e + ".mid.attn_1", cur, dev, self.attn_flash),
                       VResBlock(sd, e + ".mid.block_2", cur, cur, dev))
         self.e_norm = prep_norm(sd, e + ".norm_out", dev)
         self.e_out = prep_conv3x3(sd, e + ".conv_out", dev)
@@ -103,7 +154,7 @@ class AutoencoderKL:
         cur = ch * mult[-1]
         self.d_in = prep_conv3x3(sd, d + ".conv_in", dev)
         self.d_in_pad = self.d_in[0].shape[1] // 9
-        self.d_mid = (VResBlock(sd, d + ".mid.block_1", cur, cur, dev), VAttn(sd, d + ".mid.attn_1", cur, dev),
+        self.d_mid = (VResBlock(sd, d + ".mid.block_1", cur, cur, dev), VAttn(sd, d + ".mid.attn_1", cur, dev, self.attn_flash),
                       VResBlock(sd, d + ".mid.block_2", cur, cur, dev))
         self.d_up = []
         for lvl in reversed(range(len(mult))):
@@ -132,6 +183,7 @@ class AutoencoderKL:
         down = 2 ** (len(self.dd["ch_mult"]) - 1)
         if H % down or W % down:   # the (0,1,0,1)-padded stride-2 stages and the decoder's exact x2 (model.py:67-71,46-52) round-trip only these
             raise ValueError(f"AutoencoderKL: image height and width must be multiples of {down}, got {H}x{W}")
+        attn_plan(self.dd["ch"] * self.dd["ch_mult"][-1], (H // down) * (W // down), self.attn_flash)   # refuse up front what the mid block cannot run
         step = self._frames_per_call(H, W)
         if N > step:  # frames are independent: chunk so every operand fits the addressing window
             parts = [self.moments(x[i:i + step]) for i in range(0, N, step)]
@@ -169,6 +221,7 @@ class AutoencoderKL:
     def decode(self, z, scale=1.0):
         """z [N,4,h,w] float -> image [N,3,8h,8w] fp32 (autoencoder.py:97-100); z is multiplied by ``scale`` first."""
         N, C, h, w = z.shape
+        attn_plan(self.dd["ch"] * self.dd["ch_mult"][-1], h * w, self.attn_flash)   # refuse up front what the mid block cannot run
         step = self._frames_per_call(8 * h, 8 * w)
         if N > step:
             return torch.cat([self.decode(z[i:i + step], scale) for i in range(0, N, step)], 0)
