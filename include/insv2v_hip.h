@@ -174,6 +174,36 @@ int64_t insv2v_set_operand_window(int64_t bytes);
 int insv2v_gemm_stats_parts(const insv2v_gemm_desc* d);
 /* 1 if insv2v_gemm would run this CONV3X3 problem on the patch-tiled kernel, i.e. accepts gn_ab; else 0. */
 int insv2v_conv3x3_fuses_groupnorm(const insv2v_gemm_desc* d);
+/* What insv2v_gemm does with a descriptor, without doing it: the answer of the one planner (csrc/gemm_plan.h) that insv2v_gemm,
+ * insv2v_gemm_stats_parts and insv2v_conv3x3_fuses_groupnorm all consult.  A pure function of the descriptor's integers, the null /
+ * alignment bits of its pointers, the CU count, the operand window in force and the INSV2V_* A/B switches; it touches no GPU.
+ * A purely additive entry of ABI 14: no existing struct or entry changes. */
+#define INSV2V_PLAN_NONE 0 /* refused (rc != 0) */
+#define INSV2V_PLAN_TILE 1 /* gemm_kernel: variant = tile shape 1..9, ring = LDS ring depth 2..4 */
+#define INSV2V_PLAN_HALO 2 /* patch-tiled conv_halo_kernel: variant 0 = product, 1..3 = the A/B configurations of tile codes 101..103 */
+#define INSV2V_PLAN_Q8 3   /* gemm_q8 256x256, gemm_r8 256x320, gemm_w4 128x256 / 256x128: variant = the engine's variant argument */
+#define INSV2V_PLAN_R8 4
+#define INSV2V_PLAN_W4 5
+typedef struct insv2v_gemm_plan_t {
+    int32_t rc;             /* 0, or what insv2v_gemm returns without launching anything (INSV2V_EINVAL / INSV2V_EUNSUPPORTED); with parts > 1 it speaks
+                             * for the first part: a smaller last part is planned when it runs and may still be refused */
+    int32_t family;         /* INSV2V_PLAN_* */
+    int32_t variant;
+    int32_t ring;
+    int32_t tw_shift;       /* HALO: log2 of the patch width; | 256 with the legacy tile map */
+    int32_t cim;            /* R8: the convolution walks K channel-block-major */
+    int32_t split_k;        /* split-K factor of the tile kernel, 1 = none */
+    int32_t ln_finalize;    /* an ln_finalize launch (partial row statistics -> (mean, rstd)) precedes the kernel */
+    int32_t splitk_reduce;  /* a splitk_reduce launch follows it */
+    int32_t stats_width;    /* columns per statistics part this problem emits with stats_out set: 0 (cannot), 64, 128 or 160 */
+    int32_t gn_fuse;        /* CONV3X3: the kernel this problem runs on with gn_ab set normalises its own input */
+    int32_t parts;          /* 1, or the number of in-window parts of a problem beyond the operand window: every part is planned on its own, ... */
+    int32_t units_per_part; /* ... of this many rows (LINEAR) / images (CONV3X3), the last maybe fewer; the fields above are the first part's plan */
+    int32_t forced_tile;    /* the `tile` code that forces this choice (same split_k, <= 1 for the engines): 1..9 + 10 x ring, 100..103, 210 + variant, 230 + variant, 240 + variant */
+} insv2v_gemm_plan_t;
+/* cus <= 0: this device's CU count (0 without a GPU: the rules that weigh rounds of tiles then choose nothing).  Returns INSV2V_EINVAL
+ * for a NULL argument, else 0 with *out filled - also when out->rc says the problem is refused. */
+int insv2v_gemm_plan(const insv2v_gemm_desc* d, int cus, insv2v_gemm_plan_t* out);
 
 /*
  * Winograd F(2x2, 3x3) form of a stride-1, pad-1 3x3 convolution (ResnetBlock3D conv1 / conv2 with wide inputs, resnet.py:143,159 behind

@@ -696,13 +696,8 @@ static int launch_short(const insv2v_attention_desc& d, hipStream_t s) {
     // persistent over problems (see the kernel: the bias fragments are read once per wave): a few workgroups per CU, problems dealt round-robin
     // so that workgroups running side by side read neighbouring token rows.  INSV2V_ATTN_SHORT_WGS = workgroups per CU (0: one per problem).
     static const int wgs_per_cu = getenv("INSV2V_ATTN_SHORT_WGS") ? atoi(getenv("INSV2V_ATTN_SHORT_WGS")) : 2;
-    static int cus = 0;
-    if (!cus) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return INSV2V_EINVAL;
-        cus = prop.multiProcessorCount;
-    }
+    const int cus = insv2v_num_cus();
+    if (cus <= 0) return INSV2V_EINVAL;
     const int grid = (wgs_per_cu > 0 && d.q_bias) ? (int)std::min<int64_t>(d.batch, (int64_t)cus * wgs_per_cu) : d.batch;
     if (d.q_bias) hipLaunchKernelGGL((attn_short_kernel<D, true>), dim3(grid), dim3(d.heads * 64), lds, s, d);
     else hipLaunchKernelGGL((attn_short_kernel<D>), dim3(grid), dim3(d.heads * 64), lds, s, d);

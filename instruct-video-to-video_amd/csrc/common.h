@@ -99,6 +99,9 @@ static inline hipStream_t as_stream(insv2v_stream_t s) { return (hipStream_t)s; 
 // call with compare-exchange - instead of one unsynchronised static per translation unit.)
 bool insv2v_one_device_check();
 static inline bool one_device() { return insv2v_one_device_check(); }
+// The CU count of that device, read once for the library (elementwise.hip, next to the latch).  0 if it cannot be read: a launcher that
+// sizes a persistent grid by it answers INSV2V_EINVAL, a dispatch rule that weighs rounds of tiles chooses nothing.
+int insv2v_num_cus();
 // The window set by insv2v_set_operand_window (gemm.hip), 0 if none: the launchers that split a problem into in-window ranges obey it.
 int64_t insv2v_operand_window_override();
 static inline int launch_status() {

@@ -627,6 +627,17 @@ bool insv2v_one_device_check() {
     }
     return true;
 }
+int insv2v_num_cus() {
+    static std::atomic<int> cus{-1};   // -1: not asked yet; 0: asked, and there is no device to ask
+    int n = cus.load();
+    if (n < 0) {
+        int dev = 0;
+        hipDeviceProp_t prop;
+        n = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ? prop.multiProcessorCount : 0;
+        cus.store(n);
+    }
+    return n;
+}
 extern "C" int insv2v_init(void) {
     int dev = 0;
     hipError_t e = hipGetDevice(&dev);

@@ -32,6 +32,8 @@
 #include "common.h"
 #include <algorithm>
 #include "gemm_dma.h"
+#include "gemm_plan.h"
+static_assert(GEMM_BK == BK, "gemm_plan.h restates the K slice");
 #include <type_traits>
 #include <cstdlib>
 
@@ -848,52 +850,26 @@ static int launch_halo(const insv2v_gemm_desc& d, int tw_shift, hipStream_t s) {
     constexpr size_t stage = (size_t)BM * (BN + 4) * sizeof(float);
     constexpr size_t lds = (ring > stage ? ring : stage) + (size_t)BN * sizeof(float) + (GN ? 1024 : 0);
     static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute((const void*)conv_halo_kernel<WM, WN, MI, NI, KG, GN, WS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return (int)e;
-        attr_set = true;
-    }
+    if (const int e = set_dynamic_lds(attr_set, (const void*)conv_halo_kernel<WM, WN, MI, NI, KG, GN, WS>, lds)) return e;
     const int tiles = d.NB * (d.OH * d.OW / BM) * ((d.N + BN - 1) / BN);
-    static const int legacy_map = getenv("INSV2V_HALO_LEGACY_MAP") ? atoi(getenv("INSV2V_HALO_LEGACY_MAP")) : 0;
-    if (legacy_map) tw_shift |= 256;
     hipLaunchKernelGGL((conv_halo_kernel<WM, WN, MI, NI, KG, GN, WS>), dim3(tiles), dim3(WM * WN * KG * 64), lds, s, d, tw_shift);
     return launch_status();
-}
-
-// patch geometry of the halo kernel for this problem: log2(TW), or -1 when it does not apply
-static int halo_tw_shift(const insv2v_gemm_desc& d) {
-    if (d.mode != INSV2V_MODE_CONV3X3 || d.stride != 1 || d.pad_t != 1 || d.pad_l != 1 || (d.Cin % BK) || d.batch > 1) return -1;
-    if (d.k_split > 0 && (d.k_split % BK)) return -1;
-    if (d.row_stats || d.rb_mod > 0 || d.act == INSV2V_ACT_GEGLU) return -1;
-    const int up = d.upsample ? 2 : 1;
-    if (d.OH != d.IH * up || d.OW != d.IW * up) return -1;
-    if (d.OH % 8 == 0 && d.OW % 16 == 0) return 4;   // 8 x 16 patch
-    if (d.OH % 16 == 0 && d.OW % 8 == 0) return 3;   // 16 x 8 patch
-    return -1;
 }
 
 template <int WM, int WN, int MI, int NI, int MODE, int STAGES, int KG = 1>
 static int launch_cfg(const insv2v_gemm_desc& d, hipStream_t s) {
     constexpr int BM = WM * MI * 32, BN = WN * NI * 32;
-    constexpr size_t ring = (size_t)STAGES * (BM + BN) * BK * sizeof(half_t);
-    constexpr size_t stage = (size_t)BM * (BN + 4) * sizeof(float);
-    constexpr size_t lds = (ring > stage ? ring : stage) + (size_t)(2 * BN + 2 * BM) * sizeof(float);
-    if (lds > 160 * 1024) return INSV2V_EUNSUPPORTED;
+    constexpr size_t lds = tile_lds_bytes(BM, BN, STAGES);
+    if (lds > TILE_LDS_MAX) return INSV2V_EUNSUPPORTED;   // (plan_gemm refuses such a tile code first)
     static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute((const void*)gemm_kernel<WM, WN, MI, NI, MODE, STAGES, KG>,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return (int)e;
-        attr_set = true;
-    }
+    if (const int e = set_dynamic_lds(attr_set, (const void*)gemm_kernel<WM, WN, MI, NI, MODE, STAGES, KG>, lds)) return e;
     int tiles = ((d.M + BM - 1) / BM) * ((d.N + BN - 1) / BN);
     dim3 grid(tiles, d.batch > 0 ? d.batch : 1, d.split_k > 1 ? d.split_k : 1);
     hipLaunchKernelGGL((gemm_kernel<WM, WN, MI, NI, MODE, STAGES, KG>), grid, dim3(WM * WN * KG * 64), lds, s, d);
     return launch_status();
 }
 
-// tile shapes: 1 = 128x128, 2 = 64x128, 3 = 128x64, 4 = 64x64 (4 waves); 5 = 128x128, 6 = 256x128, 7 = 128x64 (8 waves);
-// 8 = 128x128, 9 = 128x64 (8 waves as 2 K groups of 4)
+// tile shapes: gemm_plan.h (tile_bm / tile_bn restate the sizes these template arguments give)
 template <int MODE, int STAGES>
 static int dispatch_tile(const insv2v_gemm_desc& d, int tile, hipStream_t s) {
     switch (tile) {
@@ -908,24 +884,6 @@ static int dispatch_tile(const insv2v_gemm_desc& d, int tile, hipStream_t s) {
         case 9: return launch_cfg<2, 2, 2, 1, MODE, STAGES, 2>(d, s);  // 128x64,  2 K groups of 4 waves
     }
     return INSV2V_EINVAL;
-}
-
-static int pick_tile(const insv2v_gemm_desc& d) {
-    // Measured on MI355X (tools/bench_gemm.py, profiles/): the kernel is bound by memory latency x the LDS
-    // capacity available for slices in flight, so wave-level parallelism decides: the 8-wave 128x128 tile
-    // (2 workgroups = 16 waves per CU) wins whenever it yields >= ~200 workgroups; tiny problems
-    // (M = 1152 at the lowest UNet level) use 64x64 tiles (4-5 workgroups/CU).
-    // GEGLU needs each wave to own an [h|g] pair of 32-row weight blocks (NI = 2): tiles 5 / 2.
-    const long batch = d.batch > 0 ? d.batch : 1;
-    auto blocks = [&](int bm, int bn) { return (long)((d.M + bm - 1) / bm) * ((d.N + bn - 1) / bn) * batch; };
-    const long b11 = blocks(128, 128);
-    if (d.act == INSV2V_ACT_GEGLU) return b11 >= 200 ? 5 : 2;
-    if (d.mode == INSV2V_MODE_CONV3X3) return (b11 >= 200 && d.N >= 128) ? 5 : 4;
-    // Round 2 re-check (profiles/r02_ring_depth_tile_sweep.txt): in ISOLATION the 64x64 tile wins on the single-branch N = C GEMMs
-    // (1536 x 1280 x 1280 + residual 15.0 vs 19.3 us, 24 576 x 320 x 320 17.8 vs 20.1 us), but a rule that picked it there made the
-    // 3-stream UNet step SLOWER (-2.7 % vs -4.3 % against the same baseline): three branches' kernels overlap, and many small
-    // workgroups crowd the other branches' tiles out.  Deeper LDS rings (tile codes 3x / 4x) lose wherever they cost a workgroup per CU.
-    return blocks(128, 64) >= 200 ? 5 : 4;
 }
 
 // Split-K second pass: out = epilogue(sum_s partial[s]) with the same epilogue semantics as the main
@@ -996,7 +954,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(insv2v_gemm_desc p, 
     }
 }
 
-// (mean, rstd) pairs from the producer's partial sums, for the kernels that park finished statistics (gemm_p8 / gemm_w4)
+// (mean, rstd) pairs from the producer's partial sums, for the kernels that park finished statistics (gemm_q8 / gemm_r8 / gemm_w4)
 __global__ __launch_bounds__(256) void ln_finalize_kernel(const float2* parts, float2* stats, int M, int nparts, int C, float eps) {
     const int m = blockIdx.x * 256 + threadIdx.x;
     if (m >= M) return;
@@ -1006,113 +964,17 @@ __global__ __launch_bounds__(256) void ln_finalize_kernel(const float2* parts, f
     stats[m] = make_float2(mean, rsqrtf(fmaxf(s2 / C - mean * mean, 0.f) + eps));
 }
 
-// Persistent big-tile kernels (gemm_p8.hip: 256x256, one 8-wave workgroup per CU; gemm_w4.hip: 128x256, two 4-wave
-// workgroups per CU) for the linear shapes where they measured faster than the 128x128 tile on MI355X
-// (tools/gemm_check, profiles/r02_gemm_check_*.txt; both the 3-branch batched and the single-branch token counts):
-// the GEGLU FF1 and the fused q/k/v projections, i.e. wide-N GEMMs without a residual.  GEMMs with a residual
-// (N = C) and every convolution stay on the 2-workgroup 128x128 / halo kernels, whose four waves per SIMD overlap
-// the epilogue with the next tile.  Returns 0 = no, 1 = p8, 2 = w4.
-// Round 4: which of the two 8-wave ping-pong kernels (gemm_q8: 256x256, gemm_r8: 256x320) - if any - runs a linear GEMM without
-// activation or a convolution.  Every UNet width is a multiple of 320, so gemm_r8 has no partial column tiles where gemm_q8 has
-// (N = 320 / 640 / 960 / 1920); what decides is how the tile count quantises over the CUs (persistent grids: rounds of tiles), against
-// the finer-grained round-1 kernels (128x128 tiles / patch-tiled conv, two workgroups per CU) at ~0.8 of the new engine's rate
-// (tools/gemm_check --set unet30: profiles/r04_gemm_r8_unet30.txt).  Returns 0 = neither, 1 = gemm_q8, 2 = gemm_r8.
-static int num_cus_gemm() {
-    static int cus = 0;
-    if (!cus) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return 0;
-        cus = prop.multiProcessorCount;
-    }
-    return cus;
-}
-static int pick_pingpong(const insv2v_gemm_desc& d) {
-    static const int enabled = getenv("INSV2V_GEMM_R8") ? atoi(getenv("INSV2V_GEMM_R8")) : 1;
-    static int cus = 0;
-    if (!enabled || d.act != INSV2V_ACT_NONE || d.batch > 1 || d.c_fp32 || d.M < 8192 || d.N < 256) return 0;
-    // statistics of the output rows: only gemm_r8's LINEAR form emits them (two 160-column partial sums per tile row)
-    static const int r8_stats = getenv("INSV2V_R8_STATS") ? atoi(getenv("INSV2V_R8_STATS")) : 1;
-    if (d.stats_out && (!r8_stats || d.mode != INSV2V_MODE_LINEAR || d.k_split || (d.N % 320))) return 0;
-    if (d.mode == INSV2V_MODE_LINEAR && d.K < 256) return 0;
-    if (d.row_bias && ((d.ld_rb & 3) || (d.rows_per_group % 256 && d.M > d.rows_per_group))) return 0;
-    if (!cus) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return 0;
-        cus = prop.multiProcessorCount;
-    }
-    const long tm = (d.M + 255) / 256;
-    const double old_cost = (double)tm * d.N / cus / 0.80;
-    const long q_tiles = tm * ((d.N + 255) / 256), r_tiles = tm * ((d.N + 319) / 320);
-    const double q_cost = (double)((q_tiles + cus - 1) / cus) * 256 * 1.03, r_cost = (double)((r_tiles + cus - 1) / cus) * 320;
-    // (only the UNet's widths: the VAE's 128 / 256 / 512-channel convolutions stay where round 3 measured them)
-    if (d.N % 320 == 0 && (r_cost <= q_cost || d.stats_out) && r_cost < old_cost) return 2;
-    // (INSV2V_Q8_MIN_N: the narrowest output gemm_q8 takes by dispatch; round 6: 256, i.e. the VAE's 256 / 512-channel
-    //  convolutions on the 16x16x32 engine: profiles/r06_vae_q8_ab.txt)
-    static const int q8_min_n = getenv("INSV2V_Q8_MIN_N") ? atoi(getenv("INSV2V_Q8_MIN_N")) : 256;
-    if (d.N % 256 == 0 && d.N >= q8_min_n && (d.N % 320 != 0 || q_cost < r_cost) && q_cost < old_cost && d.K >= 1152 && !d.stats_out) return 1;
-    return 0;
-}
-static int pick_persistent(const insv2v_gemm_desc& d) {
-    static const int enabled = getenv("INSV2V_GEMM_PERSISTENT") ? atoi(getenv("INSV2V_GEMM_PERSISTENT")) : 1;
-    if (!enabled || d.mode != INSV2V_MODE_LINEAR || d.batch > 1 || d.c_fp32 || d.k_split) return 0;
-    // the persistent kernels park ONE row-bias vector per tile: every 256-row tile must lie inside one bias group
-    if (d.row_bias && ((d.ld_rb & 3) || (d.rows_per_group % 256 && d.M > d.rows_per_group))) return 0;
-    // Round 3 (stacked clips, M = 23 040 ... 92 160 at levels 1-2): with K >= 1280 the 256x256 kernel's epilogue is amortised and it
-    // wins with or without a residual - FF2 23 040 x 1 280 x 5 120 358 vs 424 us, q/k/v 23 040 x 3 840 x 1 280 259 vs 325 us, FF2
-    // 92 160 x 640 x 2 560 462 vs 482 us; at the single-clip sizes (M*N below ~2e7) the 128x128 tile stays ahead
-    // (tools/bench_tiles_r03.py, profiles/r03_tile_sweep_stacked.txt)
-    if (d.act == INSV2V_ACT_NONE && d.K >= 1280 && d.N >= 640 && (int64_t)d.M * d.N >= (int64_t)20 << 20) return 1;
-    if (d.residual) return 0;
-    if (d.act == INSV2V_ACT_GEGLU) {
-        if (d.K <= 320) return d.M >= 8192 ? 2 : 0;
-        return d.M >= 1024 ? 1 : 0;
-    }
-    if (d.act != INSV2V_ACT_NONE || d.N < 960 || d.K > 640 || d.M < 4096) return 0;
-    if (d.M >= 12288) return 2;
-    return d.K == 640 ? 1 : 2;
-}
-
-// Automatic split-K: only for problems that cannot fill the chip (fewer than ~1 workgroup per CU with
-// 128x128 tiles) and whose K is long enough that every split still runs >= 16 slices.
-static int pick_split(const insv2v_gemm_desc& d) {
-    if (d.split_k == 1 || !d.workspace || d.batch > 1 || d.act == INSV2V_ACT_GEGLU || (d.N & 7) || d.row_stats || d.rb_mod > 0) return 1;
-    const long b11 = (long)((d.M + 127) / 128) * ((d.N + 127) / 128);
-    const int nk = (d.K + BK - 1) / BK;
-    int s = d.split_k;
-    if (s == 0) {
-        if (b11 >= 200 || nk < 64) return 1;
-        s = (int)(512 / b11);
-        if (s > nk / 16) s = nk / 16;
-        if (s > 8) s = 8;
-    }
-    if (s < 2) return 1;
-    if ((int64_t)s * d.M * d.N * 4 > d.workspace_bytes) return 1;
-    return s;
-}
-
-// Column-tile width of the kernel that will run a statistics-emitting GEMM (0 = cannot emit): such a problem always takes the
-// round-1 tile kernel's vectorised fp16 epilogue, no split-K, no persistent kernel.
-static int stats_tile_width(const insv2v_gemm_desc& d) {
-    if (d.mode != INSV2V_MODE_LINEAR || d.c_fp32 || d.act == INSV2V_ACT_GEGLU || d.batch > 1 || (d.N & 7) || (d.ldc & 7) ||
-        ((uintptr_t)d.c & 15) || (d.residual && ((d.ldr & 7) || ((uintptr_t)d.residual & 15) || (int64_t)d.M * d.ldr * 2 >= ((int64_t)1 << 31))))
-        return 0;
-    int shape = d.tile % 10;
-    if (d.tile >= 240 && d.tile <= 249) return (d.N % 320 || d.k_split) ? 0 : 160;   // gemm_r8 forced
-    if (d.tile >= 100) return 0;
-    if (d.tile == 0) {   // what the dispatch would do with a statistics-emitting problem
-        insv2v_gemm_desc dd = d;
-        if (!dd.stats_out) dd.stats_out = (float*)(uintptr_t)16;
-        if (dd.batch <= 0) dd.batch = 1;
-        if (pick_pingpong(dd) == 2) return 160;
-    }
-    if (shape == 0) shape = pick_tile(d);
-    switch (shape) {
-        case 1: case 2: case 5: case 6: case 8: return 128;
-        case 3: case 4: case 7: case 9: return 64;
-    }
-    return 0;
+// The A/B switches of the GEMM path (gemm_plan.h), read from the environment once for the library.
+const gemm_switches& insv2v_gemm_switches() {
+    static const gemm_switches sw = [] {
+        auto env = [](const char* name, int dflt) { const char* v = getenv(name); return v ? atoi(v) : dflt; };
+        gemm_switches s;
+        s.r8 = env("INSV2V_GEMM_R8", s.r8); s.r8_stats = env("INSV2V_R8_STATS", s.r8_stats); s.q8_min_n = env("INSV2V_Q8_MIN_N", s.q8_min_n); s.persistent = env("INSV2V_GEMM_PERSISTENT", s.persistent);
+        s.r8_geglu = env("INSV2V_R8_GEGLU", s.r8_geglu); s.r8_cim = env("INSV2V_R8_CIM", s.r8_cim); s.halo_legacy_map = env("INSV2V_HALO_LEGACY_MAP", s.halo_legacy_map);
+        s.r8_dephase = env("INSV2V_R8_DEPHASE", s.r8_dephase); s.w4_wgs = env("INSV2V_W4_WGS", s.w4_wgs); s.w4_delay = env("INSV2V_W4_DELAY", s.w4_delay);
+        return s;
+    }();
+    return sw;
 }
 
 // Bytes of one operand window of insv2v_gemm (0 = the hardware's: 2 GiB less a margin).  Tests shrink it so that small problems take the
@@ -1125,266 +987,82 @@ extern "C" int64_t insv2v_set_operand_window(int64_t bytes) {
 }
 static int64_t operand_window() { return g_operand_window > 0 ? g_operand_window : ((int64_t)1 << 31) - ((int64_t)1 << 20); }
 int64_t insv2v_operand_window_override() { return g_operand_window; }   // (the row launchers split by the same hook: rows_common.h)
-// Does an operand of this problem reach beyond one window (insv2v_gemm then runs it as row / image ranges, without output statistics)?
-// One helper for insv2v_gemm and insv2v_gemm_stats_parts, so that the two cannot disagree.
-static bool beyond_window(const insv2v_gemm_desc& d) {
-    const bool conv = d.mode == INSV2V_MODE_CONV3X3;
-    const int64_t a_rows = conv ? (int64_t)d.NB * d.IH * d.IW : (int64_t)d.M;
-    const int64_t esz = d.c_fp32 ? 4 : 2;
-    const int64_t big_in = std::max(a_rows * d.lda * 2, d.k_split ? a_rows * d.lda2 * 2 : (int64_t)0);
-    const int64_t big_out = std::max((int64_t)d.M * d.ldc * esz, d.residual ? (int64_t)d.M * d.ldr * 2 : (int64_t)0);
-    return big_in >= operand_window() || big_out >= operand_window();
-}
 
-extern "C" int insv2v_gemm_stats_parts(const insv2v_gemm_desc* dp) {
-    if (!dp) return 0;
-    insv2v_gemm_desc d = *dp;
-    if (d.batch <= 0) d.batch = 1;
-    if (beyond_window(d)) return 0;   // a split problem emits no statistics: say so before the caller allocates for them
-    const int w = stats_tile_width(d);
-    return w ? (d.N + w - 1) / w : 0;
+// ONE planner (gemm_plan.h) answers for the launch and for the three read-only entries, so that they cannot disagree
+static insv2v_gemm_plan_t plan_here(const insv2v_gemm_desc& d, int cus = 0, bool queries_only = false) {
+    return plan_gemm(d, cus > 0 ? cus : insv2v_num_cus(), operand_window(), insv2v_gemm_switches(), queries_only);
 }
+extern "C" int insv2v_gemm_plan(const insv2v_gemm_desc* dp, int cus, insv2v_gemm_plan_t* out) {
+    if (!dp || !out) return INSV2V_EINVAL;
+    *out = plan_here(*dp, cus);
+    return 0;
+}
+extern "C" int insv2v_gemm_stats_parts(const insv2v_gemm_desc* dp) {
+    const int w = dp ? plan_here(*dp, 0, true).stats_width : 0;
+    return w ? (dp->N + w - 1) / w : 0;
+}
+extern "C" int insv2v_conv3x3_fuses_groupnorm(const insv2v_gemm_desc* dp) { return dp ? plan_here(*dp, 0, true).gn_fuse : 0; }
 
 // the persistent kernels park finished (mean, rstd) pairs: partial sums from a producer are finalised by a small launch first
-static insv2v_gemm_desc finished_stats_of(insv2v_gemm_desc dd, hipStream_t s) {
-    if (dd.stats_parts > 0) {
-        hipLaunchKernelGGL(ln_finalize_kernel, dim3((dd.M + 255) / 256), dim3(256), 0, s, (const float2*)dd.row_stats,
-                           (float2*)dd.stats_scratch, dd.M, dd.stats_parts, dd.K, dd.ln_eps);
-        dd.row_stats = dd.stats_scratch; dd.stats_parts = 0;
+static void finish_stats(insv2v_gemm_desc& d, hipStream_t s) {
+    hipLaunchKernelGGL(ln_finalize_kernel, dim3((d.M + 255) / 256), dim3(256), 0, s, (const float2*)d.row_stats, (float2*)d.stats_scratch, d.M,
+                       d.stats_parts, d.K, d.ln_eps);
+    stats_finished(d);
+}
+
+// one in-window problem, as planned
+static int execute(insv2v_gemm_desc d, const insv2v_gemm_plan_t& p, hipStream_t s) {
+    if (p.ln_finalize) finish_stats(d, s);
+    const insv2v_gemm_desc full = d;
+    if (p.split_k > 1) splitk_main_pass(d, p.split_k);
+    else d.split_k = 1;
+    const bool conv = d.mode == INSV2V_MODE_CONV3X3;
+    int rc = INSV2V_EINVAL;
+    switch (p.family) {
+        case INSV2V_PLAN_Q8: return insv2v_gemm_q8(d, p.variant, s);
+        case INSV2V_PLAN_R8: return insv2v_gemm_r8(d, p.variant, s);
+        case INSV2V_PLAN_W4: return insv2v_gemm_w4(d, p.variant, s);
+        case INSV2V_PLAN_HALO:
+            switch (p.variant) {
+                case 0: return d.gn_ab ? launch_halo<4, 2, 1, 2, 1, true>(d, p.tw_shift, s) : launch_halo<4, 2, 1, 2, 1>(d, p.tw_shift, s);
+                case 3: return launch_halo<8, 2, 1, 2, 1, false, 3>(d, p.tw_shift, s);  // ONE 16-wave workgroup per CU, for A/B measurement
+                case 2: return launch_halo<2, 2, 2, 2, 1>(d, p.tw_shift, s);            // 4 waves with 64 x 64 wave tiles, for A/B measurement
+                case 1: return launch_halo<2, 2, 2, 2, 2>(d, p.tw_shift, s);            // K-group variant, kept for A/B measurement
+            }
+            return rc;
+        case INSV2V_PLAN_TILE:
+            // (An L2 prefetch of slices 3 steps ahead was measured and removed: 30-45 % slower, profiles/README.md.)
+            switch (p.ring) {
+                case 2: rc = conv ? dispatch_tile<INSV2V_MODE_CONV3X3, 2>(d, p.variant, s) : dispatch_tile<INSV2V_MODE_LINEAR, 2>(d, p.variant, s); break;
+                case 3: rc = conv ? dispatch_tile<INSV2V_MODE_CONV3X3, 3>(d, p.variant, s) : dispatch_tile<INSV2V_MODE_LINEAR, 3>(d, p.variant, s); break;
+                case 4: rc = conv ? dispatch_tile<INSV2V_MODE_CONV3X3, 4>(d, p.variant, s) : dispatch_tile<INSV2V_MODE_LINEAR, 4>(d, p.variant, s); break;
+            }
+            if (rc != 0 || !p.splitk_reduce) return rc;
+            hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)(((int64_t)full.M * (full.N / 8) + 255) / 256)), dim3(256), 0, s, full, (const float*)full.workspace, p.split_k);
+            return launch_status();
     }
-    return dd;
+    return rc;
+}
+
+static int run(const insv2v_gemm_desc& d, hipStream_t s);
+// a problem beyond the operand window: p.parts launches over row (LINEAR) / image (CONV3X3) ranges, each planned on its own
+static int run_parts(insv2v_gemm_desc f, const insv2v_gemm_plan_t& p, hipStream_t s) {
+    if (p.ln_finalize) finish_stats(f, s);
+    const int64_t total = f.mode == INSV2V_MODE_CONV3X3 ? f.NB : f.M, per = p.units_per_part;
+    for (int64_t u0 = 0; u0 < total; u0 += per)
+        if (const int rc = run(window_part(f, u0, std::min(per, total - u0)), s)) return rc;
+    return 0;
+}
+static int run(const insv2v_gemm_desc& d, hipStream_t s) {
+    const insv2v_gemm_plan_t p = plan_here(d);
+    return p.rc ? p.rc : p.parts > 1 ? run_parts(d, p, s) : execute(d, p, s);
 }
 
 extern "C" int insv2v_gemm(const insv2v_gemm_desc* dp, insv2v_stream_t stream) {
-    if (!one_device()) return INSV2V_EINVAL;
-    if (!dp) return INSV2V_EINVAL;
+    if (!one_device() || !dp) return INSV2V_EINVAL;
     insv2v_gemm_desc d = *dp;
-    if (!d.a || !d.w || !d.c || d.M <= 0 || d.N <= 0 || d.K <= 0) return INSV2V_EINVAL;
-    if ((d.K & 7) || (d.lda & 7) || (d.ldw & 7)) return INSV2V_EINVAL;
-    if (((uintptr_t)d.a | (uintptr_t)d.w) & 15) return INSV2V_EINVAL;
-    if (d.k_split) {
-        if (!d.a2 || (d.k_split % BK) || (d.lda2 & 7) || ((uintptr_t)d.a2 & 15)) return INSV2V_EINVAL;
-    }
-    if (d.row_bias && d.rows_per_group <= 0) return INSV2V_EINVAL;
-    if (d.row_stats && (!d.col_sum || d.batch > 1)) return INSV2V_EINVAL;
-    if (d.stats_parts < 0 || (d.stats_parts > 0 && (!d.row_stats || !d.stats_scratch))) return INSV2V_EINVAL;
-    if (d.stats_out && stats_tile_width(d) == 0) return INSV2V_EUNSUPPORTED;
-    if (d.act == INSV2V_ACT_GEGLU && (d.N % 64)) return INSV2V_EINVAL;
-    if (d.act < 0 || d.act > INSV2V_ACT_TANH) return INSV2V_EINVAL;                                   // unknown activation code
-    // (ReLU / sigmoid / tanh - the optical-flow network's - live in the 128x128 tile kernel's epilogue and the split-K reduction, for both modes;
-    //  the patch-tiled and ping-pong kernels never see those codes: the dispatch below keeps such a call away from them)
-    if (d.batch <= 0) d.batch = 1;
-    if (d.alpha == 0.f) d.alpha = 1.f;
-    if (d.w_group_rows < 0 || (d.w_group_rows > 0 && (d.w_group_rows % 256 || d.w_group_stride <= 0))) return INSV2V_EINVAL;
-    if (d.w_group_rows > 0) {   // grouped weights: the 256-row ping-pong kernels only, nothing riding in the epilogue
-        if (d.mode != INSV2V_MODE_LINEAR || d.batch > 1 || d.c_fp32 || d.act != INSV2V_ACT_NONE || d.residual || d.row_bias || d.row_stats || d.stats_out ||
-            d.k_split || d.split_k > 1 || d.K < 256 || (d.N % 256 && d.N % 320))
-            return INSV2V_EUNSUPPORTED;
-    }
-    if (d.gn_ab && (d.mode != INSV2V_MODE_CONV3X3 || d.gn_images_per_sample <= 0 || d.upsample)) return INSV2V_EINVAL;
-    if (d.mode == INSV2V_MODE_CONV3X3) {
-        if (d.Cin <= 0 || (d.Cin % BK) || d.K != 9 * d.Cin) return INSV2V_EINVAL;
-        if ((long)d.NB * d.OH * d.OW != d.M || d.stride < 1) return INSV2V_EINVAL;
-        // nearest-x2 upsample to an explicit output size (Upsample3D's output_size, resnet.py:41-61): the x2 image or that image without its last
-        // row / column; the gather kernels zero-pad at the REQUESTED extent, and index >> 1 of any tap inside it is inside the input
-        if (d.upsample && (d.stride != 1 || d.pad_t != 1 || d.pad_l != 1 || (d.OH != 2 * d.IH && d.OH != 2 * d.IH - 1) || (d.OW != 2 * d.IW && d.OW != 2 * d.IW - 1)))
-            return INSV2V_EINVAL;
-    } else if (d.mode != INSV2V_MODE_LINEAR) {
-        return INSV2V_EUNSUPPORTED;
-    }
-    // LDS-DMA addressing uses 32-bit byte offsets against a 2 GiB descriptor window per operand.  A problem whose activations, output or
-    // residual reach beyond one window runs as several launches over row ranges (LINEAR) / image ranges (CONV3X3: images are independent),
-    // every part inside the window and aligned to the row-bias / GroupNorm groups, so that every kernel family keeps its 32-bit offsets
-    // (round 5; the Python wrapper used to cut convolutions only).  Statistics of the output (stats_out: part-major with stride M) are not
-    // emitted by a split problem: the caller gets INSV2V_EUNSUPPORTED and takes the statistics pass, as for any problem that cannot emit them.
-    {
-        const bool conv = d.mode == INSV2V_MODE_CONV3X3;
-        const int64_t lim = operand_window();
-        if ((int64_t)d.N * d.ldw * 2 >= ((int64_t)1 << 31)) return INSV2V_EUNSUPPORTED;
-        const int64_t esz = d.c_fp32 ? 4 : 2;
-        if (beyond_window(d)) {
-            if (d.batch > 1 || d.stats_out || d.split_k > 1) return INSV2V_EUNSUPPORTED;
-            insv2v_gemm_desc f = finished_stats_of(d, as_stream(stream));   // partial row statistics are finalised over the whole problem first
-            auto lcm = [](int64_t a, int64_t b) { int64_t x = a, y = b; while (y) { const int64_t t = x % y; x = y; y = t; } return a / x * b; };
-            const int64_t opix = conv ? (int64_t)d.OH * d.OW : 1, ipix = conv ? (int64_t)d.IH * d.IW : 1;   // output / input rows per unit
-            int64_t unit = conv ? 1 : 2;                                                                 // images (conv) / rows (linear) per part: a multiple of this
-            if (d.row_bias) {
-                const int64_t grp = (int64_t)d.rows_per_group * (d.rb_mod > 0 ? d.rb_mod : 1);         // rows after which the bias pattern repeats / moves on
-                if (conv && grp % opix) return INSV2V_EUNSUPPORTED;
-                unit = lcm(unit, conv ? grp / opix : grp);
-            }
-            if (conv && d.gn_ab) unit = lcm(unit, d.gn_images_per_sample);
-            if (!conv && unit < 256) unit = lcm(unit, 256);                                             // whole tiles where nothing else decides
-            if (f.w_group_rows > 0) unit = lcm(unit, f.w_group_rows);                                   // grouped weights: whole groups per part
-            const int64_t total = conv ? d.NB : d.M;
-            const int64_t in_row = std::max((int64_t)d.lda * 2, d.k_split ? (int64_t)d.lda2 * 2 : (int64_t)0) * ipix;
-            const int64_t out_row = std::max((int64_t)d.ldc * esz, d.residual ? (int64_t)d.ldr * 2 : (int64_t)0) * opix;
-            int64_t per = (lim - 1) / std::max(in_row, out_row) / unit * unit;
-            if (per <= 0) return INSV2V_EUNSUPPORTED;
-            // parts as even as possible (every distinct part size is its own dispatch decision, equal sizes share it)
-            const int64_t nparts = (total + per - 1) / per;
-            per = ((total + nparts - 1) / nparts + unit - 1) / unit * unit;
-            for (int64_t u0 = 0; u0 < total; u0 += per) {
-                const int64_t nu = std::min(per, total - u0);
-                insv2v_gemm_desc s = f;
-                const int64_t r_in = u0 * ipix, r_out = u0 * opix;
-                s.a = (const char*)f.a + r_in * f.lda * 2;
-                if (f.k_split) s.a2 = (const char*)f.a2 + r_in * f.lda2 * 2;
-                s.c = (char*)f.c + r_out * f.ldc * esz;
-                if (f.residual) s.residual = (const char*)f.residual + r_out * f.ldr * 2;
-                if (f.row_stats) s.row_stats = f.row_stats + r_out * 2;
-                if (f.w_group_rows > 0) s.w = (const char*)f.w + (r_out / f.w_group_rows) * f.w_group_stride * 2;
-                if (f.row_bias && f.rb_mod <= 0) s.row_bias = f.row_bias + (r_out / f.rows_per_group) * f.ld_rb;
-                if (conv && f.gn_ab) s.gn_ab = f.gn_ab + (u0 / f.gn_images_per_sample) * (int64_t)f.Cin * 2;
-                s.M = (int32_t)(nu * opix);
-                if (conv) s.NB = (int32_t)nu;
-                const int rc = insv2v_gemm(&s, stream);
-                if (rc != 0) return rc;
-            }
-            return 0;
-        }
-    }
-    if (d.w_group_rows > 0) {   // grouped weights (validated above): gemm_r8 / gemm_q8 by the rounds of tiles each needs
-        const int64_t groups = ((int64_t)d.M + d.w_group_rows - 1) / d.w_group_rows;
-        if (groups * d.w_group_stride * 2 >= ((int64_t)1 << 31)) return INSV2V_EUNSUPPORTED;
-        const int cus = num_cus_gemm();
-        const long tm = (d.M + 255) / 256, q_tiles = tm * ((d.N + 255) / 256), r_tiles = tm * ((d.N + 319) / 320);
-        const bool r_ok = d.N % 320 == 0, q_ok = d.N % 256 == 0;
-        const double q_cost = (double)((q_tiles + cus - 1) / cus) * 256 * 1.03, r_cost = (double)((r_tiles + cus - 1) / cus) * 320;
-        const bool use_r = d.tile / 10 == 24 ? true : d.tile / 10 == 23 ? false : (r_ok && (!q_ok || r_cost <= q_cost));
-        if (use_r ? !r_ok : !q_ok) return INSV2V_EUNSUPPORTED;
-        return use_r ? insv2v_gemm_r8(d, 0, as_stream(stream)) : insv2v_gemm_q8(d, 0, as_stream(stream));
-    }
-    // tile code: low digit = tile shape (0 auto), tens digit = ring depth S (0 default = 2, or 2 / 3).
-    // (An L2 prefetch of slices 3 steps ahead was measured and removed: 30-45 % slower, profiles/README.md.)
-    auto finished_stats = [&](const insv2v_gemm_desc& dd) { return finished_stats_of(dd, as_stream(stream)); };
-    if (d.tile >= 200 && d.tile <= 206) return INSV2V_EUNSUPPORTED;  // round 3's 256x256 kernel (gemm_p8): retired in round 6, source kept under tools/archive/
-    if (d.tile >= 230 && d.tile <= 239) {  // 256x256 8-phase kernel, interleaved half-tile ownership (gemm_q8.hip), forced
-        if (d.split_k > 1 || d.stats_out) return INSV2V_EUNSUPPORTED;
-        d.split_k = 1;
-        return insv2v_gemm_q8(finished_stats(d), d.tile - 230, as_stream(stream));
-    }
-    if (d.tile >= 240 && d.tile <= 249) {  // 256x320 tile on the round-4 engine (gemm_r8.hip), forced
-        if (d.split_k > 1) return INSV2V_EUNSUPPORTED;
-        d.split_k = 1;
-        return insv2v_gemm_r8(finished_stats(d), d.tile - 240, as_stream(stream));
-    }
-    if (d.tile >= 210 && d.tile <= 221) {  // 4-wave persistent kernel (gemm_w4.hip), forced: 210 = 128x256, 211 = 256x128
-        if (d.split_k > 1 || d.stats_out) return INSV2V_EUNSUPPORTED;
-        d.split_k = 1;
-        return insv2v_gemm_w4(finished_stats(d), d.tile - 210, as_stream(stream));
-    }
-    int shape = d.tile % 10, pipe = d.tile / 10;
-    const int nsplit = d.stats_out ? 1 : pick_split(d);
-    insv2v_gemm_desc full = d;
-    if (nsplit > 1) {  // main pass: raw fp32 partial slabs [nsplit, M, N] in the workspace, no epilogue
-        d.c = d.workspace; d.ldc = d.N; d.c_fp32 = 1; d.c_bs = 0;
-        d.bias = nullptr; d.row_bias = nullptr; d.residual = nullptr; d.act = INSV2V_ACT_NONE; d.alpha = 1.f;
-        d.row_stats = nullptr; d.col_sum = nullptr;
-        d.split_k = nsplit;
-        if (shape == 0) shape = 5;
-    } else {
-        d.split_k = 1;
-    }
-    if (nsplit <= 1 && d.tile == 0 && !d.gn_ab) {   // (with stats_out: gemm_r8 or nothing, pick_pingpong)
-        const int pp = pick_pingpong(d);
-        if (pp) {
-            const insv2v_gemm_desc dd = finished_stats(d);
-            const int rc = pp == 2 ? insv2v_gemm_r8(dd, 0, as_stream(stream)) : insv2v_gemm_q8(dd, 0, as_stream(stream));
-            // (a statistics buffer sized for gemm_r8's 160-column parts must not reach a kernel with another part width)
-            if (rc != INSV2V_EUNSUPPORTED || d.stats_out) return rc;
-        }
-    }
-    if (nsplit <= 1 && d.tile == 0 && !d.stats_out && d.act == INSV2V_ACT_GEGLU && d.mode == INSV2V_MODE_LINEAR && !d.k_split && !d.residual) {
-        // Round 4: the GEGLU FF1 of levels 1-3 (N = 5120 / 10240 = whole 320-row tiles) on the 256x320 kernel where its rounds of tiles
-        // cost no more than the 256x256 kernel's: 7 % faster at K = 640, 3.5 % at K = 1280 (profiles/r04_gemm_r8_geglu.txt)
-        static const int r8_geglu = getenv("INSV2V_R8_GEGLU") ? atoi(getenv("INSV2V_R8_GEGLU")) : 1;
-        const int cus = num_cus_gemm();
-        if (r8_geglu && cus > 0 && d.N % 320 == 0 && d.M >= 8192 && d.K >= 640 && !d.c_fp32 && d.batch <= 1) {
-            const long tm = (d.M + 255) / 256, q_tiles = tm * ((d.N + 255) / 256), r_tiles = tm * (d.N / 320);
-            const double q_cost = (double)((q_tiles + cus - 1) / cus) * 256 * 1.03, r_cost = (double)((r_tiles + cus - 1) / cus) * 320;
-            if (r_cost <= q_cost) {
-                const int rc = insv2v_gemm_r8(finished_stats(d), 0, as_stream(stream));
-                if (rc != INSV2V_EUNSUPPORTED) return rc;
-            }
-        }
-    }
-    if (nsplit <= 1 && d.tile == 0 && !d.stats_out) {
-        const int pick = pick_persistent(d);
-        if (pick) {
-            // eligibility is static (shape / alignment): an EUNSUPPORTED answer comes before any launch of the kernel itself
-            const insv2v_gemm_desc dd = finished_stats(d);
-            // (N = 640 - FF2 of level 1 - is 2.5 column tiles of the 256x256 kernel; running the last 128 columns on the 128x128 tile as a
-            //  second launch was built and measured: no gain end to end, profiles/r03_gemm_split_columns_experiment.txt)
-            // round 4: the 256x256 choice runs on gemm_q8 (interleaved half-tile ownership, LDS-DMA inside the MFMA segments, concurrent
-            // epilogues): 8-25 % faster than gemm_p8 on every UNet shape (profiles/r04_gemm_q8_vs_p8.txt)
-            const int rc = pick == 1 ? insv2v_gemm_q8(dd, 0, as_stream(stream)) : insv2v_gemm_w4(dd, 0, as_stream(stream));
-            if (rc != INSV2V_EUNSUPPORTED) return rc;
-        }
-    }
-    if (nsplit <= 1 && (d.tile == 100 || d.tile == 0)) {
-        const int tws = halo_tw_shift(d);
-        if (d.tile == 100 && tws < 0) return INSV2V_EUNSUPPORTED;
-        if (d.tile == 100 && d.act >= INSV2V_ACT_RELU) return INSV2V_EUNSUPPORTED;
-        if (tws >= 0 && d.act < INSV2V_ACT_RELU && (d.tile == 100 || ((long)d.M / 128) * ((d.N + 127) / 128) >= 200))
-            return d.gn_ab ? launch_halo<4, 2, 1, 2, 1, true>(d, tws, as_stream(stream)) : launch_halo<4, 2, 1, 2, 1>(d, tws, as_stream(stream));
-    }
-    if (d.gn_ab) return INSV2V_EUNSUPPORTED;  // only the patch-tiled kernel normalises its input (never silently skip the norm)
-    // Round 3: convolutions the patch kernel cannot tile (8x12 / 4x6 latents, stride 2) at the stacked-clip sizes: the 256x256 persistent
-    // kernel beats the gathered 128x128 tile once M fills it (23 040 x 1 280 x 11 520: 712 vs 838 us, x 23 040: 1 357 vs 1 597 us;
-    // at M = 4 608 it loses 340 vs 192 us, at M = 5 760 320 vs 206 us, at M = 11 520 (10 stacked clips at the 4x6 level) it wins 330 vs 384 us -
-    // tools/bench_conv_tiles_r03.py, profiles/r03_conv_tile_sweep_stacked.txt, r03_conv_tile_sweep_B30.txt)
-    if (nsplit <= 1 && d.tile == 0 && d.mode == INSV2V_MODE_CONV3X3 && d.batch == 1 && !d.c_fp32 && d.M >= 10240 && d.N >= 640 && d.K >= 5760) {
-        static const int enabled = getenv("INSV2V_GEMM_PERSISTENT") ? atoi(getenv("INSV2V_GEMM_PERSISTENT")) : 1;
-        if (enabled) {
-            const int rc = insv2v_gemm_q8(d, 0, as_stream(stream));
-            if (rc != INSV2V_EUNSUPPORTED) return rc;
-        }
-    }
-    if (d.tile >= 101 && d.tile <= 103 && d.act >= INSV2V_ACT_RELU) return INSV2V_EUNSUPPORTED;
-    if (nsplit <= 1 && d.tile == 103) {  // ONE 16-wave workgroup per CU on a 256-pixel patch, weight slices requested two taps ahead, for A/B measurement
-        int tws = halo_tw_shift(d);
-        if (tws < 0 || d.gn_ab) return INSV2V_EUNSUPPORTED;
-        if (d.OH % 16 == 0 && d.OW % 16 == 0) tws = 4;          // 16 x 16 patch
-        else if (d.OH % 32 == 0 && d.OW % 8 == 0) tws = 3;      // 32 x 8 patch
-        else return INSV2V_EUNSUPPORTED;
-        return launch_halo<8, 2, 1, 2, 1, false, 3>(d, tws, as_stream(stream));
-    }
-    if (nsplit <= 1 && d.tile == 102) {  // 4 waves with 64 x 64 wave tiles (1 KB of LDS reads per MFMA instead of 1.5), for A/B measurement
-        const int tws = halo_tw_shift(d);
-        if (tws < 0 || d.gn_ab) return INSV2V_EUNSUPPORTED;
-        return launch_halo<2, 2, 2, 2, 1>(d, tws, as_stream(stream));
-    }
-    if (nsplit <= 1 && d.tile == 101) {  // K-group variant, kept for A/B measurement
-        const int tws = halo_tw_shift(d);
-        if (tws < 0) return INSV2V_EUNSUPPORTED;
-        return launch_halo<2, 2, 2, 2, 2>(d, tws, as_stream(stream));
-    }
-    if (shape == 0) shape = pick_tile(d);
-    if (d.act == INSV2V_ACT_GEGLU && (shape == 3 || shape == 4 || shape == 7 || shape == 9)) shape = 2;
-    if (pipe == 0) pipe = 2;
-    hipStream_t s = as_stream(stream);
-    const bool conv = d.mode == INSV2V_MODE_CONV3X3;
-    int rc = INSV2V_EINVAL;
-    switch (pipe) {
-        case 2: rc = conv ? dispatch_tile<INSV2V_MODE_CONV3X3, 2>(d, shape, s) : dispatch_tile<INSV2V_MODE_LINEAR, 2>(d, shape, s); break;
-        case 3: rc = conv ? dispatch_tile<INSV2V_MODE_CONV3X3, 3>(d, shape, s) : dispatch_tile<INSV2V_MODE_LINEAR, 3>(d, shape, s); break;
-        case 4: rc = conv ? dispatch_tile<INSV2V_MODE_CONV3X3, 4>(d, shape, s) : dispatch_tile<INSV2V_MODE_LINEAR, 4>(d, shape, s); break;
-    }
-    if (rc != 0 || nsplit <= 1) return rc;
-    const int64_t nchunk = (int64_t)full.M * (full.N / 8);
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((nchunk + 255) / 256)), dim3(256), 0, s, full, (const float*)full.workspace, nsplit);
-    return launch_status();
-}
-
-extern "C" int insv2v_conv3x3_fuses_groupnorm(const insv2v_gemm_desc* dp) {
-    if (!dp || dp->mode != INSV2V_MODE_CONV3X3 || dp->upsample || dp->split_k > 1) return 0;
-    insv2v_gemm_desc d = *dp;
-    if (d.batch <= 0) d.batch = 1;
-    if (d.tile != 0 && d.tile != 100) return 0;
-    if (halo_tw_shift(d) < 0) return 0;
-    if (d.tile == 0 && (pick_split(d) > 1 || ((long)d.M / 128) * ((d.N + 127) / 128) < 200)) return 0;
-    return 1;
+    gemm_defaults(d);
+    return run(d, as_stream(stream));
 }
 
 #ifdef INSV2V_GEMM_PROF

@@ -1,4 +1,4 @@
-// LDS-DMA helpers shared by the GEMM kernels (gemm.hip, gemm_p8.hip).
+// LDS-DMA helpers shared by the GEMM kernels (gemm.hip, gemm_q8.hip, gemm_r8.hip, gemm_w4.hip) and the row kernels.
 #pragma once
 #include "common.h"
 
@@ -19,10 +19,18 @@ __device__ __forceinline__ void wait_vmcnt() {
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 
-// internal entry of the 8-phase 256x256 kernel (gemm_p8.hip); INSV2V_EUNSUPPORTED when the problem is not eligible
-// internal entry of the round-4 8-phase kernel with interleaved half-tile ownership (gemm_q8.hip); same eligibility as gemm_p8
+// the dynamic-LDS attribute of a kernel, set on its first launch (done: the launcher's latch); 0 or the HIP error
+static inline int set_dynamic_lds(bool& done, const void* kernel, size_t bytes) {
+    if (done) return 0;
+    const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    done = e == hipSuccess;
+    return (int)e;
+}
+
+// The three persistent engines' internal entries.  Each refuses (INSV2V_EUNSUPPORTED / INSV2V_EINVAL) by its predicate in gemm_plan.h.
+// the 8-phase 256x256 kernel with interleaved half-tile ownership (gemm_q8.hip)
 int insv2v_gemm_q8(const insv2v_gemm_desc& d, int variant, hipStream_t s);
-// internal entry of the 256 x 320 tile form of the round-4 engine (gemm_r8.hip): LINEAR / CONV3X3, no activation
+// the 256 x 320 tile form of the same engine (gemm_r8.hip)
 int insv2v_gemm_r8(const insv2v_gemm_desc& d, int variant, hipStream_t s);
-// internal entry of the 4-wave, two-workgroups-per-CU persistent kernel (gemm_w4.hip)
+// the 4-wave, two-workgroups-per-CU persistent kernel (gemm_w4.hip)
 int insv2v_gemm_w4(const insv2v_gemm_desc& d, int variant, hipStream_t s);

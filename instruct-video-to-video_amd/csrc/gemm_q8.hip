@@ -33,6 +33,7 @@
 // stores, hazard workarounds) is gemm_p8's; see that file for the reasoning.
 #include "common.h"
 #include "gemm_dma.h"
+#include "gemm_plan.h"
 #include <type_traits>
 
 namespace {
@@ -490,16 +491,9 @@ __global__ __launch_bounds__(512) void gemm_q8_kernel(insv2v_gemm_desc p) {
 template <int MODE, bool GEGLU, bool HAS_RES, int DBG = 0, int VAR = 0>
 int launch_q8(const insv2v_gemm_desc& d, hipStream_t s) {
     static bool attr_set = false;
-    static int num_cu = 0;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute((const void*)gemm_q8_kernel<MODE, GEGLU, HAS_RES, DBG, VAR>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_B + STAMP_B);
-        if (e != hipSuccess) return (int)e;
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return INSV2V_EINVAL;
-        num_cu = prop.multiProcessorCount;
-        attr_set = true;
-    }
+    if (const int e = set_dynamic_lds(attr_set, (const void*)gemm_q8_kernel<MODE, GEGLU, HAS_RES, DBG, VAR>, LDS_B + STAMP_B)) return e;
+    const int num_cu = insv2v_num_cus();
+    if (num_cu <= 0) return INSV2V_EINVAL;
     const int tiles = ((d.M + 255) / 256) * ((d.N + 255) / 256);
     hipLaunchKernelGGL((gemm_q8_kernel<MODE, GEGLU, HAS_RES, DBG, VAR>), dim3(tiles < num_cu ? tiles : num_cu), dim3(512), LDS_B + (DBG == 4 ? STAMP_B : 0), s, d);
     return launch_status();
@@ -507,25 +501,10 @@ int launch_q8(const insv2v_gemm_desc& d, hipStream_t s) {
 
 }  // namespace
 
-// variant: 0 = product (LDS-DMA requests inside the MFMA segments); 1 = requests in the load segments (round-4 A/B: 5-18 % slower);
-// 2 = no epilogue (timing); 3 = the two wave groups' epilogues one after the other (A/B); 4 / 5 = s_memtime stamps of schedule 1 / 0
+// variant and eligibility: q8_refusal (gemm_plan.h), which the planner asks before it sends a problem here
 int insv2v_gemm_q8(const insv2v_gemm_desc& d, int variant, hipStream_t s) {
-    if (d.batch > 1 || d.c_fp32 || d.split_k > 1) return INSV2V_EUNSUPPORTED;
-    if ((d.K % BK) || (d.N & 7) || (d.ldc & 7) || ((uintptr_t)d.c & 15)) return INSV2V_EUNSUPPORTED;
-    if (d.residual && ((d.ldr & 7) || ((uintptr_t)d.residual & 15))) return INSV2V_EUNSUPPORTED;
-    if (d.k_split && (d.k_split % BK)) return INSV2V_EUNSUPPORTED;
-    if (d.act == INSV2V_ACT_GEGLU && (d.N % 64)) return INSV2V_EUNSUPPORTED;
-    if (d.row_stats && (d.M & 1)) return INSV2V_EUNSUPPORTED;  // (mean, rstd) pairs are fetched two rows per lane
-    // the row-bias vector is parked per tile: every 256-row tile must lie inside one group
-    if (d.row_bias && ((d.ld_rb & 3) || (d.rows_per_group % 256 && d.M > d.rows_per_group))) return INSV2V_EUNSUPPORTED;
-    if ((int64_t)d.M * d.ldc * 2 >= ((int64_t)1 << 31) || (d.residual && (int64_t)d.M * d.ldr * 2 >= ((int64_t)1 << 31))) return INSV2V_EUNSUPPORTED;
-    const bool conv = d.mode == INSV2V_MODE_CONV3X3;
-    if (conv && (d.Cin % BK)) return INSV2V_EUNSUPPORTED;
-    const bool gg = d.act == INSV2V_ACT_GEGLU;
-    if (!gg && d.act != INSV2V_ACT_NONE) return INSV2V_EUNSUPPORTED;
-    if (conv && gg) return INSV2V_EUNSUPPORTED;
-    const bool res = d.residual != nullptr;
-    if (gg && res) return INSV2V_EUNSUPPORTED;
+    if (const int rc = q8_refusal(d, variant)) return rc;
+    const bool conv = d.mode == INSV2V_MODE_CONV3X3, gg = d.act == INSV2V_ACT_GEGLU, res = d.residual != nullptr;
     constexpr int L = INSV2V_MODE_LINEAR, C = INSV2V_MODE_CONV3X3;
     switch (variant) {
         case 0:
@@ -536,19 +515,12 @@ int insv2v_gemm_q8(const insv2v_gemm_desc& d, int variant, hipStream_t s) {
             if (conv) return res ? launch_q8<C, false, true, 0, 0>(d, s) : launch_q8<C, false, false, 0, 0>(d, s);
             if (gg) return launch_q8<L, true, false, 0, 0>(d, s);
             return res ? launch_q8<L, false, true, 0, 0>(d, s) : launch_q8<L, false, false, 0, 0>(d, s);
-        case 2:
-            if (conv || gg || res) return INSV2V_EUNSUPPORTED;
-            return launch_q8<L, false, false, 2, 1>(d, s);
+        case 2: return launch_q8<L, false, false, 2, 1>(d, s);
         case 3:
-            if (conv) return INSV2V_EUNSUPPORTED;
             if (gg) return launch_q8<L, true, false, 3, 1>(d, s);
             return res ? launch_q8<L, false, true, 3, 1>(d, s) : launch_q8<L, false, false, 3, 1>(d, s);
-        case 4:
-            if (conv || gg || res) return INSV2V_EUNSUPPORTED;
-            return launch_q8<L, false, false, 4, 1>(d, s);
-        case 5:
-            if (conv || gg || res) return INSV2V_EUNSUPPORTED;
-            return launch_q8<L, false, false, 4, 0>(d, s);
+        case 4: return launch_q8<L, false, false, 4, 1>(d, s);
+        case 5: return launch_q8<L, false, false, 4, 0>(d, s);
     }
     return INSV2V_EINVAL;
 }

@@ -26,8 +26,8 @@
 //  * No GEGLU (those widths are multiples of 256: gemm_q8).
 #include "common.h"
 #include "gemm_dma.h"
+#include "gemm_plan.h"
 #include <type_traits>
-#include <cstdlib>
 
 namespace {
 
@@ -636,55 +636,25 @@ __global__ __launch_bounds__(512) void gemm_r8_kernel(insv2v_gemm_desc p, int de
 template <int MODE, bool HAS_RES, int DBG = 0, bool SPLIT = true, bool STATS = false, bool GEGLU = false, bool CIM = false>
 int launch_r8(const insv2v_gemm_desc& d, hipStream_t s) {
     static bool attr_set = false;
-    static int num_cu = 0;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute((const void*)gemm_r8_kernel<MODE, HAS_RES, DBG, SPLIT, STATS, GEGLU, CIM>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_B);
-        if (e != hipSuccess) return (int)e;
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return INSV2V_EINVAL;
-        num_cu = prop.multiProcessorCount;
-        attr_set = true;
-    }
+    if (const int e = set_dynamic_lds(attr_set, (const void*)gemm_r8_kernel<MODE, HAS_RES, DBG, SPLIT, STATS, GEGLU, CIM>, LDS_B)) return e;
+    const int num_cu = insv2v_num_cus();
+    if (num_cu <= 0) return INSV2V_EINVAL;
     const int tiles = ((d.M + BM - 1) / BM) * ((d.N + BN - 1) / BN);
-    // INSV2V_R8_DEPHASE: permille of a tile time over which the workgroups with one tile to spare start late (0 = off)
-    static const int dephase = getenv("INSV2V_R8_DEPHASE") ? atoi(getenv("INSV2V_R8_DEPHASE")) : 0;
+    const int dephase = insv2v_gemm_switches().r8_dephase;
     hipLaunchKernelGGL((gemm_r8_kernel<MODE, HAS_RES, DBG, SPLIT, STATS, GEGLU, CIM>), dim3(tiles < num_cu ? tiles : num_cu), dim3(512), LDS_B, s, d, dephase);
     return launch_status();
 }
 
 }  // namespace
 
-// variant: 0 = product; 2 = no epilogue (timing)
+// variant and eligibility: r8_refusal (gemm_plan.h), which the planner asks before it sends a problem here
 int insv2v_gemm_r8(const insv2v_gemm_desc& d, int variant, hipStream_t s) {
-    if (d.batch > 1 || d.c_fp32 || d.split_k > 1) return INSV2V_EUNSUPPORTED;
-    if ((d.K % BK) || (d.N & 7) || (d.ldc & 7) || ((uintptr_t)d.c & 15)) return INSV2V_EUNSUPPORTED;
-    if (d.residual && ((d.ldr & 7) || ((uintptr_t)d.residual & 15))) return INSV2V_EUNSUPPORTED;
-    if (d.k_split && (d.k_split % BK)) return INSV2V_EUNSUPPORTED;
-    const bool geglu = d.act == INSV2V_ACT_GEGLU;
-    if (d.act != INSV2V_ACT_NONE && !geglu) return INSV2V_EUNSUPPORTED;
-    // GEGLU: W rows in [32 value | 32 gate] blocks, whole 320-row tiles (= 160 outputs), no residual / second source / statistics
-    if (geglu && (d.mode != INSV2V_MODE_LINEAR || (d.N % BN) || d.residual || d.k_split > 0 || d.stats_out || variant != 0)) return INSV2V_EUNSUPPORTED;
-    if (d.row_stats && (d.M & 1)) return INSV2V_EUNSUPPORTED;  // (mean, rstd) pairs are fetched two rows per lane
-    // the row-bias vector is parked per tile: every 256-row tile must lie inside one group
-    if (d.row_bias && ((d.ld_rb & 3) || (d.rows_per_group % 256 && d.M > d.rows_per_group))) return INSV2V_EUNSUPPORTED;
-    if ((int64_t)d.M * d.ldc * 2 >= ((int64_t)1 << 31) || (d.residual && (int64_t)d.M * d.ldr * 2 >= ((int64_t)1 << 31))) return INSV2V_EUNSUPPORTED;
-    if ((d.bias && ((uintptr_t)d.bias & 15)) || (d.col_sum && ((uintptr_t)d.col_sum & 15)) || (d.row_bias && ((uintptr_t)d.row_bias & 15)))
-        return INSV2V_EUNSUPPORTED;
-    const bool conv = d.mode == INSV2V_MODE_CONV3X3;
-    if (conv && ((d.Cin % BK) || d.M >= (1 << 24))) return INSV2V_EUNSUPPORTED;   // (row -> pixel by fp32 division: exact below 2^24 rows)
-    const bool res = d.residual != nullptr;
+    if (const int rc = r8_refusal(d, variant)) return rc;
+    const bool conv = d.mode == INSV2V_MODE_CONV3X3, res = d.residual != nullptr;
     constexpr int L = INSV2V_MODE_LINEAR, C = INSV2V_MODE_CONV3X3;
-    if (geglu) return launch_r8<L, false, 0, false, false, true>(d, s);
-    if (d.stats_out) {   // partial row statistics of the output: LINEAR, whole 320-column tiles, one A source
-        if (conv || d.k_split > 0 || (d.N % BN) || variant != 0) return INSV2V_EUNSUPPORTED;
-        return res ? launch_r8<L, true, 0, false, true>(d, s) : launch_r8<L, false, 0, false, true>(d, s);
-    }
-    // stride-1 / pad-1 convolutions (every ResnetBlock3D convolution) walk K channel-block-major (template flag CIM); INSV2V_R8_CIM=0
-    // keeps the tap-major order for A/B runs
-    static const bool cim_on = !(getenv("INSV2V_R8_CIM") && atoi(getenv("INSV2V_R8_CIM")) == 0);
-    const bool cim = conv && cim_on && d.stride == 1 && !d.upsample && d.pad_t == 1 && d.pad_l == 1 && d.IH == d.OH && d.IW == d.OW;
-    if (cim && (variant == 0 || variant == 4)) {
+    if (d.act == INSV2V_ACT_GEGLU) return launch_r8<L, false, 0, false, false, true>(d, s);
+    if (d.stats_out) return res ? launch_r8<L, true, 0, false, true>(d, s) : launch_r8<L, false, 0, false, true>(d, s);
+    if (r8_uses_cim(d, variant, insv2v_gemm_switches())) {   // K channel-block-major
         if (variant == 4) return res ? launch_r8<C, true, 4, true, false, false, true>(d, s) : launch_r8<C, false, 4, true, false, false, true>(d, s);
         if (d.k_split > 0) return res ? launch_r8<C, true, 0, true, false, false, true>(d, s) : launch_r8<C, false, 0, true, false, false, true>(d, s);
         return res ? launch_r8<C, true, 0, false, false, false, true>(d, s) : launch_r8<C, false, 0, false, false, false, true>(d, s);
@@ -697,12 +667,8 @@ int insv2v_gemm_r8(const insv2v_gemm_desc& d, int variant, hipStream_t s) {
             }
             if (conv) return res ? launch_r8<C, true, 0, false>(d, s) : launch_r8<C, false, 0, false>(d, s);
             return res ? launch_r8<L, true, 0, false>(d, s) : launch_r8<L, false, 0, false>(d, s);
-        case 2:
-            if (conv) return launch_r8<C, false, 2>(d, s);
-            return launch_r8<L, false, 2>(d, s);
-        case 5:
-            if (conv) return launch_r8<C, false, 5>(d, s);
-            return launch_r8<L, false, 5>(d, s);
+        case 2: return conv ? launch_r8<C, false, 2>(d, s) : launch_r8<L, false, 2>(d, s);
+        case 5: return conv ? launch_r8<C, false, 5>(d, s) : launch_r8<L, false, 5>(d, s);
         case 4:
             if (conv) return res ? launch_r8<C, true, 4>(d, s) : launch_r8<C, false, 4>(d, s);
             return res ? launch_r8<L, true, 4>(d, s) : launch_r8<L, false, 4>(d, s);

@@ -18,8 +18,8 @@
 //    offsets instead of branches, park vectors read with inline-asm ds_read), see the comments there.
 #include "common.h"
 #include "gemm_dma.h"
+#include "gemm_plan.h"
 #include <type_traits>
-#include <cstdlib>
 
 namespace {
 
@@ -393,20 +393,12 @@ int launch_w4(const insv2v_gemm_desc& d, hipStream_t s) {
     constexpr int BM = 32 * TM * WM, BN = 64 * WN;
     constexpr int LDS_B = 3 * (BM + BN) * 64 + 2 * PARK4_B;
     static bool attr_set = false;
-    static int num_cu = 0;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute((const void*)gemm_w4_kernel<MODE, GEGLU, HAS_RES, WM, WN, TM, DBG>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_B);
-        if (e != hipSuccess) return (int)e;
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return INSV2V_EINVAL;
-        num_cu = prop.multiProcessorCount;
-        attr_set = true;
-    }
+    if (const int e = set_dynamic_lds(attr_set, (const void*)gemm_w4_kernel<MODE, GEGLU, HAS_RES, WM, WN, TM, DBG>, LDS_B)) return e;
+    const int num_cu = insv2v_num_cus();
+    if (num_cu <= 0) return INSV2V_EINVAL;
     const int tiles = ((d.M + BM - 1) / BM) * ((d.N + BN - 1) / BN);
-    static const int dbg_wgs = getenv("INSV2V_W4_WGS") ? atoi(getenv("INSV2V_W4_WGS")) : 2;  // debugging: workgroups per CU
+    const int dbg_wgs = insv2v_gemm_switches().w4_wgs, dbg_delay = insv2v_gemm_switches().w4_delay;   // debugging: workgroups per CU, tile delay
     const int grid = tiles < dbg_wgs * num_cu ? tiles : dbg_wgs * num_cu;
-    static const int dbg_delay = getenv("INSV2V_W4_DELAY") ? atoi(getenv("INSV2V_W4_DELAY")) : -1;
     W4Args a;
     static_cast<insv2v_gemm_desc&>(a) = d;
     a.tile_delay = grid > num_cu ? dbg_delay : 0;
@@ -425,26 +417,12 @@ int dispatch_w4(const insv2v_gemm_desc& d, int dbg, hipStream_t s) {
 
 }  // namespace
 
-// variant: 0 = 128 x 256 tile (waves 1 x 4), 1 = 256 x 128 tile (waves 2 x 2); +10 = timing ablation without epilogue
+// variant and eligibility: w4_refusal (gemm_plan.h), which the planner asks before it sends a problem here
 int insv2v_gemm_w4(const insv2v_gemm_desc& d, int variant, hipStream_t s) {
-    if (d.batch > 1 || d.c_fp32 || d.split_k > 1) return INSV2V_EUNSUPPORTED;
-    if ((d.K % BK4) || d.K < 2 * BK4 || (d.N & 7) || (d.ldc & 7) || ((uintptr_t)d.c & 15)) return INSV2V_EUNSUPPORTED;
-    if (d.residual && ((d.ldr & 7) || ((uintptr_t)d.residual & 15))) return INSV2V_EUNSUPPORTED;
-    if (d.k_split && (d.k_split % BK4)) return INSV2V_EUNSUPPORTED;
-    const bool gg = d.act == INSV2V_ACT_GEGLU;
-    if (gg && ((d.N % 64) || d.residual)) return INSV2V_EUNSUPPORTED;
-    if (!gg && d.act != INSV2V_ACT_NONE) return INSV2V_EUNSUPPORTED;  // SiLU / quick-GELU GEMMs are tiny (time embedding, CLIP)
-    if (d.row_stats && (d.M & 1)) return INSV2V_EUNSUPPORTED;          // (mean, rstd) pairs are fetched two rows per lane
-    const int v = variant % 10;  // 0: 4 waves 128x256, 1: 4 waves 256x128, 2: 8 waves 128x256, 3: 8 waves 256x128
-    const int bm = (v == 1 || v == 3) ? 256 : 128;
-    if (v >= 2 && d.act == INSV2V_ACT_GEGLU) return INSV2V_EUNSUPPORTED;  // the 8-wave tiles exist for the memory-bound N = C GEMMs
-    // the row-bias vector is parked per tile: every tile must lie inside one group
-    if (d.row_bias && ((d.ld_rb & 3) || (d.rows_per_group % bm && d.M > d.rows_per_group))) return INSV2V_EUNSUPPORTED;
-    if ((int64_t)d.M * d.ldc * 2 >= ((int64_t)1 << 31) || (d.residual && (int64_t)d.M * d.ldr * 2 >= ((int64_t)1 << 31))) return INSV2V_EUNSUPPORTED;
-    const bool conv = d.mode == INSV2V_MODE_CONV3X3;
-    if (conv && ((d.Cin % BK4) || gg)) return INSV2V_EUNSUPPORTED;
+    if (const int rc = w4_refusal(d, variant)) return rc;
+    static_assert(W4_BK == BK4, "gemm_plan.h restates the K tile");
     const int dbg = variant / 10;
-    switch (v) {
+    switch (variant % 10) {
         case 0: return dispatch_w4<1, 4, 4>(d, dbg, s);
         case 1: return dispatch_w4<2, 2, 4>(d, dbg, s);
         case 2: return dispatch_w4<2, 4, 2>(d, dbg, s);

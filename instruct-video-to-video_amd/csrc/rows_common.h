@@ -269,15 +269,7 @@ __device__ __forceinline__ half8 frame_hot(int fr, int oct) {
     return f;
 }
 
-int num_cus() {
-    static int n = 0;
-    if (!n) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) n = prop.multiProcessorCount;
-    }
-    return n;
-}
+int num_cus() { return insv2v_num_cus(); }
 
 // Operands beyond one 2 GiB descriptor.  The fused kernels address x / out / residual through descriptors built at the operand's base, with
 // 32-bit lane offsets.  Their launchers run a problem whose operands reach beyond the window as RANGES OF WHOLE UNITS - 128-row tiles

@@ -33,6 +33,12 @@ class GemmDesc(C.Structure):
                 ("w_group_stride", c_i64), ("w_group_rows", c_i32), ("reserved0", c_i32)]
 
 
+class GemmPlan(C.Structure):
+    """insv2v_gemm_plan_t: what insv2v_gemm does with a descriptor (insv2v_gemm_plan; csrc/gemm_plan.h)."""
+    _fields_ = [(n, c_i32) for n in ("rc", "family", "variant", "ring", "tw_shift", "cim", "split_k", "ln_finalize", "splitk_reduce", "stats_width",
+                                     "gn_fuse", "parts", "units_per_part", "forced_tile")]
+
+
 class WinogradInDesc(C.Structure):
     _fields_ = [("x", c_p), ("x2", c_p), ("gn_ab", c_p), ("v", c_p), ("ldx", c_i64), ("ldx2", c_i64), ("v_group_rows", c_i64),
                 ("NB", c_i32), ("H", c_i32), ("W", c_i32), ("C", c_i32), ("C1", c_i32), ("gn_images_per_sample", c_i32), ("gn_silu", c_i32), ("upsample", c_i32)]
@@ -124,6 +130,7 @@ SIGNATURES = {
     "insv2v_init": (c_i32, []),
     "insv2v_gemm": (c_i32, [C.POINTER(GemmDesc), c_p]),
     "insv2v_gemm_stats_parts": (c_i32, [C.POINTER(GemmDesc)]),
+    "insv2v_gemm_plan": (c_i32, [C.POINTER(GemmDesc), c_i32, C.POINTER(GemmPlan)]),
     "insv2v_set_operand_window": (c_i64, [c_i64]),
     "insv2v_conv3x3_fuses_groupnorm": (c_i32, [C.POINTER(GemmDesc)]),
     "insv2v_winograd_input": (c_i32, [C.POINTER(WinogradInDesc), c_p]),

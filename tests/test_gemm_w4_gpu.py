@@ -485,3 +485,83 @@ def test_w4_gate_cases_run_by_dispatch(name):
     """... and where the argument set is legal for insv2v_gemm as such, the dispatched call (tile=0) succeeds and is right."""
     out, ref, ln = gate_call(name, 0)
     close(out, ref, ln, f"dispatched gemm, {name}")
+
+
+# ------------------------------------------------------------------------------------------- 6. the plan names the dispatch
+# One problem per kernel family plan_gemm (csrc/gemm_plan.h) can choose: the dispatched call (tile=0) is bit-equal to the call forced to
+# the plan's own tile code.  The first eight shapes are the smallest that were named for the rules when the planner was introduced; on
+# 256 CUs two of them stay below their rule's threshold (8192 x 640 x 256 and the 2 x 16 x 16 convolution run on the tile kernel), so
+# the smallest problems that do reach gemm_r8's linear form and the patch-tiled kernel follow them.  The convolution that reaches
+# gemm_r8's channel-block-major form is searched for with the plan itself.
+def plan_of_call(run):
+    """The plan (for this device) of the first insv2v_gemm descriptor run() issues, and run()'s result."""
+    import ctypes
+    from insv2v import _lib
+    lib, seen = _lib.load(), []
+    real = lib.insv2v_gemm
+
+    def spy(ref, stream):
+        if not seen:
+            seen.append(_lib.GemmPlan())
+            assert lib.insv2v_gemm_plan(ref, 0, ctypes.byref(seen[0])) == 0
+        return real(ref, stream)
+    lib.insv2v_gemm = spy
+    try:
+        out = run()
+    finally:
+        lib.insv2v_gemm = real
+    return seen[0], out
+
+
+def smallest_cim_conv():
+    """(NB, Cout) of the smallest 16 x 16, 64-channel convolution that plan_gemm sends to gemm_r8's CIM form on this device."""
+    import ctypes
+    from insv2v import _lib
+    lib, best, p = _lib.load(), None, _lib.GemmPlan()
+    for cout in (320, 640, 960, 1280, 1920, 2560):
+        for nb in range(1, 400):
+            d = _lib.GemmDesc()
+            d.a = d.w = d.c = 16
+            d.M, d.N, d.K, d.mode, d.lda, d.ldw, d.ldc = nb * 256, cout, 576, 1, 64, 576, cout
+            d.NB, d.IH, d.IW, d.OH, d.OW, d.Cin, d.stride, d.pad_t, d.pad_l = nb, 16, 16, 16, 16, 64, 1, 1, 1
+            assert lib.insv2v_gemm_plan(ctypes.byref(d), 0, ctypes.byref(p)) == 0
+            if p.rc == 0 and p.family == 4 and p.cim:
+                if best is None or nb * cout < best[0] * best[1]:
+                    best = (nb, cout)
+                break
+    return best
+
+
+PLAN_CASES = ["lin 8192x640x256", "geglu 8192x5120x640", "lin 4096x1024x640", "geglu 8192x2560x320", "lin 1152x1280x1280", "lin 128x128x4096",
+              "conv 2x16x16 64->128", "conv cim", "lin 16384x1280x256", "conv 100x16x16 64->128"]
+PLAN_FAMILIES = {}
+
+
+@pytest.mark.parametrize("case", PLAN_CASES)
+def test_dispatch_equals_the_plans_forced_tile(case):
+    from insv2v import ops
+    from insv2v.unet import prep_conv3x3
+    kind, _, shape = case.partition(" ")
+    if kind == "conv":
+        nb, cout = smallest_cim_conv() if shape == "cim" else (int(shape.split("x")[0]), 128)
+        x = rnd(nb, 64, 16, 16).half().float()
+        wt, b = rnd(cout, 64, 3, 3, scale=576 ** -0.5).half().float(), rnd(cout, seed=4)
+        wk, bk = prep_conv3x3({"c.weight": wt.cpu(), "c.bias": b.cpu()}, "c", dev())
+        xcl = to_cl(x)
+        run = lambda t: ops.conv3x3(xcl, (nb, 16, 16), wk, bk, tile=t)[0]
+        if nb * cout <= 1 << 16:
+            close(run(0), to_cl(conv_ref(x, wt, b, 1, False)), False, case)
+    else:
+        M, N, K = map(int, shape.split("x"))
+        a, w = rnd(M, K).half(), rnd(N, K, scale=K ** -0.5).half()
+        run = lambda t: ops.gemm(a, w, act=ops.ACT_GEGLU if kind == "geglu" else ops.ACT_NONE, tile=t)
+    plan, out = plan_of_call(lambda: run(0))
+    print(f"[plan] {case}: family {plan.family} variant {plan.variant} ring {plan.ring} split_k {plan.split_k} cim {plan.cim} forced tile {plan.forced_tile}")
+    assert plan.rc == 0 and plan.parts == 1 and plan.forced_tile > 0
+    assert torch.equal(out, run(plan.forced_tile)), f"{case}: tile=0 differs from tile={plan.forced_tile}, the plan's own code"
+    assert shape != "cim" or (plan.family == 4 and plan.cim == 1)
+    PLAN_FAMILIES[case] = plan.family
+    if len(PLAN_FAMILIES) == len(PLAN_CASES) and num_cus() == 256:   # every family the planner can choose was reached
+        assert set(PLAN_FAMILIES.values()) == {1, 2, 3, 4, 5}, PLAN_FAMILIES
+        assert PLAN_FAMILIES["geglu 8192x5120x640"] == 4 and PLAN_FAMILIES["lin 4096x1024x640"] == 3 and PLAN_FAMILIES["geglu 8192x2560x320"] == 5
+        assert PLAN_FAMILIES["lin 16384x1280x256"] == 4 and PLAN_FAMILIES["conv 100x16x16 64->128"] == 2
