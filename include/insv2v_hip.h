@@ -49,7 +49,8 @@ typedef void* insv2v_stream_t; /* hipStream_t */
 
 /* ABI version, bumped on any struct change.
  * ABI 14: seeded noise - insv2v_randn, insv2v_posterior_sample_seeded and the noise_seed / noise_stream / noise_on fields of
- * insv2v_step_desc (section "seeded noise" below holds the stream definition, which is part of this contract). */
+ * insv2v_step_desc (section "seeded noise" below holds the stream definition, which is part of this contract).
+ * ABI 15: insv2v_groupnorm_plan (an addition: no existing struct or entry changes). */
 int insv2v_abi_version(void);
 /* One-time per-process setup (kernel attributes). Safe to call repeatedly. */
 int insv2v_init(void);
@@ -408,6 +409,31 @@ typedef struct insv2v_groupnorm_desc {
     int32_t stats_only;
 } insv2v_groupnorm_desc;
 int insv2v_groupnorm(const insv2v_groupnorm_desc* d, insv2v_stream_t stream);
+/* What insv2v_groupnorm does with a descriptor, without doing it: the answer of the one planner (csrc/norm_plan.h) that insv2v_groupnorm
+ * consults before it launches.  A pure function of the descriptor's integers, the null bits of its pointers and the two A/B switches
+ * INSV2V_GN_FRAME / INSV2V_GN_FRAME_SPLIT (read once per process); it touches no GPU.  The planner enforces the whole-sample kernel's
+ * reduction contract: the channel split is halved until G % cs == 0 and nt / (G / cs) is a power of two <= 64 (every split the dispatch
+ * chooses by itself meets it; an override that does not is corrected, not run).  A purely additive entry of ABI 15: no existing struct or
+ * entry changes. */
+#define INSV2V_GN_PLAN_NONE 0       /* refused (rc != 0) */
+#define INSV2V_GN_PLAN_THREE_PASS 1 /* gn_partial, gn_finalize and (without stats_only) gn_apply */
+#define INSV2V_GN_PLAN_SMALL 2      /* gn_small<vw>: one workgroup per (sample, group) */
+#define INSV2V_GN_PLAN_FRAME 3      /* gn_frame<nt>: one workgroup per (sample, channel part) */
+typedef struct insv2v_groupnorm_plan_t {
+    int32_t rc;             /* 0, or what insv2v_groupnorm returns without launching anything (INSV2V_EINVAL / INSV2V_EUNSUPPORTED) */
+    int32_t family;         /* INSV2V_GN_PLAN_* */
+    int32_t nt;             /* FRAME: threads per workgroup, 256 / 512 / 1024 */
+    int32_t cs;             /* FRAME: channel parts per sample (grid y) */
+    int32_t vw;             /* SMALL: halfs per load, 8 or 4 */
+    int32_t p;              /* THREE_PASS: token lanes per workgroup, 1..16 */
+    int32_t threads;        /* threads per workgroup of the kernel(s) that read x */
+    int32_t nchunks;        /* THREE_PASS: the descriptor's nchunks clamped to rows_per_sample (the layout of `partials`); else 1 */
+    int32_t rows_per_chunk; /* THREE_PASS: rows per chunk of pass 1 (trailing chunks may be empty); else rows_per_sample */
+    int32_t apply_grid_x;   /* grid x of the launch that writes y: THREE_PASS gn_apply (0 with stats_only), SMALL G, FRAME nsamples */
+    int32_t lds_bytes;      /* LDS per workgroup of the kernel that reads x */
+} insv2v_groupnorm_plan_t;
+/* Returns INSV2V_EINVAL for a NULL argument, else 0 with *out filled - also when out->rc says the problem is refused. */
+int insv2v_groupnorm_plan(const insv2v_groupnorm_desc* d, insv2v_groupnorm_plan_t* out);
 
 /*
  * LayerNorm over the channel axis of a token matrix [rows, C] (fp16 in/out, fp32 statistics,

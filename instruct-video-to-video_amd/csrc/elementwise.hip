@@ -610,7 +610,7 @@ extern "C" int insv2v_tap_gather(const float* y9, int64_t ld9, const float* bias
     return launch_status();
 }
 
-extern "C" int insv2v_abi_version(void) { return 14; }
+extern "C" int insv2v_abi_version(void) { return 15; }
 // The process's device (one process per GPU): latched once, by insv2v_init or by the first launcher that asks.
 static std::atomic<int> g_first_device{-1};
 bool insv2v_one_device_check() {

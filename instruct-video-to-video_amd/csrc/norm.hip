@@ -7,11 +7,13 @@
 // sample's first token) merged with Chan's parallel formula, which is deterministic (no
 // atomics) and free of the E[x^2]-E[x]^2 cancellation.
 #include "common.h"
+#include "norm_plan.h"
 #include <cstdlib>
 
 struct Moments {  // count, mean, sum of squared deviations
     float n, mean, m2;
 };
+static_assert(sizeof(Moments) == GN_MOMENTS_BYTES, "norm_plan.h restates the size");
 __device__ __forceinline__ Moments merge(Moments a, Moments b) {
     if (b.n == 0.f) return a;
     if (a.n == 0.f) return b;
@@ -184,6 +186,7 @@ __global__ void gn_apply_kernel(insv2v_groupnorm_desc p, int CC, int P) {
 // rows x cpg elements in registers (<= 256 threads x GNS_MAXCH chunks), two-pass statistics in fp32, one read
 // and one write of the tensor instead of 2 reads + 1 write over three launches.  VW = halfs per chunk.
 #define GNS_MAXCH 16
+static_assert(GNS_MAXCH == GN_SMALL_MAXCH, "norm_plan.h restates the chunks per thread");
 template <int VW>
 __global__ __launch_bounds__(256) void gn_small_kernel(insv2v_groupnorm_desc p) {
     typedef half_t vec_t __attribute__((ext_vector_type(VW)));
@@ -273,6 +276,7 @@ __global__ __launch_bounds__(256) void gn_small_kernel(insv2v_groupnorm_desc p) 
 // exactly one group (cpg % 8 == 0); its sum goes to part[chunk]; the NT / G threads of a group add that group's R x cpg / 8 entries
 // and finish with a shuffle.  Two passes over the registers (mean, then centred squares): cancellation-free like the other kernels.
 #define GNF_MAXCH 15
+static_assert(GNF_MAXCH == GN_FRAME_MAXCH, "norm_plan.h restates the chunks per thread");
 template <int NT>
 __global__ __launch_bounds__(NT) void gn_frame_kernel(insv2v_groupnorm_desc p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -381,77 +385,55 @@ __global__ __launch_bounds__(NT) void gn_frame_kernel(insv2v_groupnorm_desc p) {
 }
 
 template <int NT>
-static int launch_gn_frame(const insv2v_groupnorm_desc& d, hipStream_t s, int CS = 1) {
-    const size_t lds = ((size_t)d.rows_per_sample * (d.C / CS / 8) + 2 * (d.G / CS) + 2 * (d.C / CS)) * sizeof(float);
+static int launch_gn_frame(const insv2v_groupnorm_desc& d, hipStream_t s, const insv2v_groupnorm_plan_t& pl) {
     static bool attr_set = false;
     if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute((const void*)gn_frame_kernel<NT>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
+        hipError_t e = hipFuncSetAttribute((const void*)gn_frame_kernel<NT>, hipFuncAttributeMaxDynamicSharedMemorySize, GN_FRAME_LDS_MAX);
         if (e != hipSuccess) return (int)e;
         attr_set = true;
     }
-    if (lds > 96 * 1024) return INSV2V_EUNSUPPORTED;
-    hipLaunchKernelGGL(gn_frame_kernel<NT>, dim3(d.nsamples, CS), dim3(NT), lds, s, d);
+    hipLaunchKernelGGL(gn_frame_kernel<NT>, dim3(d.nsamples, pl.cs), dim3(NT), pl.lds_bytes, s, d);
     return launch_status();
+}
+
+// The A/B switches of the GroupNorm dispatch (norm_plan.h), read from the environment once for the library.
+static const groupnorm_switches& insv2v_groupnorm_switches() {
+    static const groupnorm_switches sw = [] {
+        auto env = [](const char* name, int dflt) { const char* v = getenv(name); return v ? atoi(v) : dflt; };
+        groupnorm_switches s;
+        s.frame = env("INSV2V_GN_FRAME", s.frame); s.split = env("INSV2V_GN_FRAME_SPLIT", s.split);
+        return s;
+    }();
+    return sw;
+}
+
+// ONE planner (norm_plan.h) answers for the launch and for the read-only entry, so that they cannot disagree
+extern "C" int insv2v_groupnorm_plan(const insv2v_groupnorm_desc* dp, insv2v_groupnorm_plan_t* out) {
+    if (!dp || !out) return INSV2V_EINVAL;
+    *out = plan_groupnorm(*dp, insv2v_groupnorm_switches());
+    return 0;
 }
 
 extern "C" int insv2v_groupnorm(const insv2v_groupnorm_desc* dp, insv2v_stream_t stream) {
     if (!one_device()) return INSV2V_EINVAL;
     if (!dp) return INSV2V_EINVAL;
     insv2v_groupnorm_desc d = *dp;
-    if (!d.x || !d.gamma || !d.beta || !d.partials) return INSV2V_EINVAL;
-    if (d.stats_only ? !d.ab : !d.y) return INSV2V_EINVAL;
-    if (d.C <= 0 || d.G <= 0 || (d.C % d.G) || (d.C & 7) || d.C > 8192) return INSV2V_EINVAL;
-    if ((d.ldx & 7) || (d.ldy & 7) || d.nsamples <= 0 || d.rows_per_sample <= 0) return INSV2V_EINVAL;
-    if (d.x2 && ((d.C1 & 7) || d.C1 <= 0 || d.C1 >= d.C || (d.ldx2 & 7))) return INSV2V_EINVAL;
-    if (d.nchunks <= 0) return INSV2V_EINVAL;
+    const insv2v_groupnorm_plan_t pl = plan_groupnorm(d, insv2v_groupnorm_switches());
+    if (pl.rc) return pl.rc;
     hipStream_t s = as_stream(stream);
-    {   // whole samples of <= 245 KB (the per-frame GroupNorm of the 8x12 / 4x6 levels), many of them: one workgroup per sample
-        static const int frame_on = getenv("INSV2V_GN_FRAME") ? atoi(getenv("INSV2V_GN_FRAME")) : 1;
-        const int cpg = d.C / d.G;
-        const int64_t nchunk = (int64_t)d.rows_per_sample * (d.C / 8);
-        if (frame_on && !d.stats_only && !d.ab && !d.x2 && (cpg % 8) == 0 && d.nsamples >= 128 && nchunk >= 2048 && nchunk <= 1024 * GNF_MAXCH &&
-            (d.G == 32 || d.G == 16) && d.C <= 2560) {
-            // channel split CS (see the kernel): as many parts as keep whole groups, a power-of-two thread count per group and >= 2048 chunks
-            // per workgroup.  INSV2V_GN_FRAME_SPLIT overrides (1 = the round-5 form: one workgroup per sample)
-            static const int split_env = getenv("INSV2V_GN_FRAME_SPLIT") ? atoi(getenv("INSV2V_GN_FRAME_SPLIT")) : 0;
-            int CS = split_env > 0 ? split_env : (nchunk > 512 * GNF_MAXCH ? 4 : nchunk > 256 * GNF_MAXCH ? 2 : 1);
-            while (CS > 1 && (d.G % CS || nchunk / CS < 1024)) CS >>= 1;
-            const int64_t nc = nchunk / CS;
-            const int rc = nc <= 256 * GNF_MAXCH ? launch_gn_frame<256>(d, s, CS) : nc <= 512 * GNF_MAXCH ? launch_gn_frame<512>(d, s, CS) : launch_gn_frame<1024>(d, s, CS);
-            if (rc != INSV2V_EUNSUPPORTED) return rc;
-        }
+    if (pl.family == INSV2V_GN_PLAN_FRAME)
+        return pl.nt == 256 ? launch_gn_frame<256>(d, s, pl) : pl.nt == 512 ? launch_gn_frame<512>(d, s, pl) : launch_gn_frame<1024>(d, s, pl);
+    if (pl.family == INSV2V_GN_PLAN_SMALL) {
+        if (pl.vw == 8) hipLaunchKernelGGL(gn_small_kernel<8>, dim3(d.G, d.nsamples), dim3(256), 0, s, d);
+        else hipLaunchKernelGGL(gn_small_kernel<4>, dim3(d.G, d.nsamples), dim3(256), 0, s, d);
+        return launch_status();
     }
-    {   // small slabs: one launch, one read + one write (cpg*2 B >= 32 B keeps the strided row pieces sector-sized)
-        const int cpg = d.C / d.G;
-        const int vw = (cpg % 8 == 0) ? 8 : ((cpg % 4 == 0) ? 4 : 0);
-        const bool src_ok = !d.x2 || (d.C1 % (vw ? vw : 1) == 0);
-        if (!d.stats_only && !d.ab && vw && cpg >= 16 && cpg <= 256 && src_ok && (int64_t)d.rows_per_sample * (cpg / vw) <= 256 * GNS_MAXCH) {
-            if (vw == 8) hipLaunchKernelGGL(gn_small_kernel<8>, dim3(d.G, d.nsamples), dim3(256), 0, s, d);
-            else hipLaunchKernelGGL(gn_small_kernel<4>, dim3(d.G, d.nsamples), dim3(256), 0, s, d);
-            return launch_status();
-        }
-    }
-    const int CC = d.C / 8;
-    if (CC > 1024) return INSV2V_EUNSUPPORTED;
-    int P = 256 / CC;
-    if (P < 1) P = 1;
-    if (P > 16) P = 16;
-    const int threads = CC * P;
-    int nchunks = d.nchunks;
-    if (nchunks > d.rows_per_sample) nchunks = d.rows_per_sample;
-    d.nchunks = nchunks;
-    const int rows_per_chunk = (d.rows_per_sample + nchunks - 1) / nchunks;
-    // a trailing chunk may be empty when rows do not divide: it contributes n = 0.
-    size_t lds = (size_t)P * d.C * sizeof(Moments);
-    if (lds > 64 * 1024) return INSV2V_EUNSUPPORTED;
-    hipLaunchKernelGGL(gn_partial_kernel, dim3(nchunks, d.nsamples), dim3(threads), lds, s, d, CC, P, rows_per_chunk);
+    const int CC = d.C / 8, P = pl.p;
+    d.nchunks = pl.nchunks;
+    hipLaunchKernelGGL(gn_partial_kernel, dim3(pl.nchunks, d.nsamples), dim3(pl.threads), pl.lds_bytes, s, d, CC, P, pl.rows_per_chunk);
     hipLaunchKernelGGL(gn_finalize_kernel, dim3((d.G + 3) / 4, d.nsamples), dim3(256), 0, s, d);
     if (d.stats_only) return launch_status();
-    long want = ((long)d.rows_per_sample + P * 4 - 1) / (P * 4);
-    long cap = 4096 / d.nsamples;
-    if (cap < 1) cap = 1;
-    int gx = (int)(want < cap ? want : cap);
-    hipLaunchKernelGGL(gn_apply_kernel, dim3(gx, d.nsamples), dim3(threads), 0, s, d, CC, P);
+    hipLaunchKernelGGL(gn_apply_kernel, dim3(pl.apply_grid_x, d.nsamples), dim3(pl.threads), 0, s, d, CC, P);
     return launch_status();
 }
 

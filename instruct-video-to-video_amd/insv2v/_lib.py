@@ -10,7 +10,7 @@ import os
 
 import torch  # noqa: F401  (must be imported first, see module docstring)
 
-ABI_VERSION = 14
+ABI_VERSION = 15
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("INSV2V_LIB", os.path.join(_HERE, "libinsv2v_hip.so"))  # override: A/B builds only
 
@@ -76,6 +76,11 @@ class GroupNormDesc(C.Structure):
                 ("ldx", c_i64), ("ldx2", c_i64), ("ldy", c_i64),
                 ("nsamples", c_i32), ("rows_per_sample", c_i32), ("C", c_i32), ("C1", c_i32), ("G", c_i32),
                 ("nchunks", c_i32), ("silu", c_i32), ("eps", c_f32), ("ab", c_p), ("stats_only", c_i32)]
+
+
+class GroupNormPlan(C.Structure):
+    """insv2v_groupnorm_plan_t: what insv2v_groupnorm does with a descriptor (insv2v_groupnorm_plan; csrc/norm_plan.h)."""
+    _fields_ = [(n, c_i32) for n in ("rc", "family", "nt", "cs", "vw", "p", "threads", "nchunks", "rows_per_chunk", "apply_grid_x", "lds_bytes")]
 
 
 class LayerNormDesc(C.Structure):
@@ -148,6 +153,7 @@ SIGNATURES = {
     "insv2v_xattn_attn": (c_i32, [C.POINTER(XattnDesc), c_p]),
     "insv2v_xattn_attn_stream_elems": (c_i64, [c_i32, c_i32, c_i32]),
     "insv2v_groupnorm": (c_i32, [C.POINTER(GroupNormDesc), c_p]),
+    "insv2v_groupnorm_plan": (c_i32, [C.POINTER(GroupNormDesc), C.POINTER(GroupNormPlan)]),
     "insv2v_layernorm": (c_i32, [C.POINTER(LayerNormDesc), c_p]),
     "insv2v_layernorm_stats": (c_i32, [c_p, c_p, c_i64, c_i32, c_i32, c_f32, c_p]),
     "insv2v_attention": (c_i32, [C.POINTER(AttentionDesc), c_p]),

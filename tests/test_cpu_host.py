@@ -50,7 +50,8 @@ def _c_struct_fields(name):
                                            ("insv2v_layernorm_desc", "LayerNormDesc"), ("insv2v_attention_desc", "AttentionDesc"),
                                            ("insv2v_step_desc", "StepDesc"), ("insv2v_im2col_desc", "Im2colDesc"),
                                            ("insv2v_corr_lookup_desc", "CorrLookupDesc"), ("insv2v_winograd_in_desc", "WinogradInDesc"),
-                                           ("insv2v_winograd_out_desc", "WinogradOutDesc"), ("insv2v_gemm_plan_t", "GemmPlan")])
+                                           ("insv2v_winograd_out_desc", "WinogradOutDesc"), ("insv2v_gemm_plan_t", "GemmPlan"),
+                                           ("insv2v_groupnorm_plan_t", "GroupNormPlan")])
 def test_ctypes_structs_mirror_the_header(cname, pyname):
     from insv2v import _lib
     want = _c_struct_fields(cname)

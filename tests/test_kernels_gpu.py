@@ -990,9 +990,11 @@ def test_groupnorm(ns, rows, C, G, silu):
                                                (256, 17, 1280, 32, False), (144, 30, 2560, 32, True), (200, 40, 640, 16, False)])
 def test_groupnorm_per_frame_whole_sample_kernel(ns, rows, C, G, silu):
     """gn_frame_kernel: many samples of <= 245 KB each (the per-frame GroupNorm in front of the spatial transformers of the 8x12 / 4x6
-    levels: 96 / 24 rows x 1280 channels) - one workgroup holds a whole sample in registers and reduces per group through LDS.  All three
-    workgroup sizes (256 / 512 / 1024 threads), ragged chunk counts, 16 and 32 groups, per-channel offsets (centred variance), SiLU;
-    a strided output/input view; and the result must not depend on how many samples the launch holds."""
+    levels: 96 / 24 rows x 1280 channels) - one workgroup holds a sample's channel part in registers and reduces per group through LDS.
+    Since the channel split every case here runs gn_frame_kernel<256> (1, 2 or 4 parts of at most 256 x 15 chunks; the 480 x 24 case
+    has 3840 chunks in one part); the 512- and 1024-thread instantiations run in tests/test_norm_stages_gpu.py, whose plan table
+    (tests/norm_ref.py) pins which kernel each case runs.  Ragged chunk counts, 16 and 32 groups, per-channel offsets (centred variance),
+    SiLU; a strided output/input view; and the result must not depend on how many samples the launch holds."""
     from insv2v import ops
     x = (rnd(ns * rows, C) * 2 + 3 * rnd(1, C, seed=2)).half()
     gamma, beta = 1 + 0.1 * rnd(C, seed=3), 0.1 * rnd(C, seed=4)

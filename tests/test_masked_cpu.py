@@ -199,7 +199,7 @@ def _c_struct_fields(header, name):
     return fields
 
 
-def test_header_and_ctypes_agree_and_abi_stays_14(tmp_path):
+def test_header_and_ctypes_agree_and_abi_is_15(tmp_path):
     from insv2v import _lib
     header = open(os.path.join(ROOT, "include", "insv2v_hip.h")).read()
     for proto in (r"int insv2v_cfg_step_mask\(const insv2v_maskstep_desc\* d, insv2v_stream_t stream\);",
@@ -212,10 +212,10 @@ def test_header_and_ctypes_agree_and_abi_stays_14(tmp_path):
     assert _lib.SIGNATURES["insv2v_mask_to_latent"] == (i32, [p, p, i32, i32, i32, i32, p])
     assert _lib.SIGNATURES["insv2v_composite"] == (i32, [p, p, p, p, i32, i32, i32, p])
     assert _lib.SIGNATURES["insv2v_add_noise"] == (i32, [p, p, p, i64, f32, f32, p])
-    # ABI 14 and the version function's text are pinned: these are additions
-    assert _lib.ABI_VERSION == 14
+    # ABI 15 and the version function's text are pinned: these are additions
+    assert _lib.ABI_VERSION == 15
     src = open(os.path.join(ROOT, "instruct-video-to-video_amd", "csrc", "elementwise.hip")).read()
-    assert re.search(r"insv2v_abi_version\(void\) \{ return 14; \}", src)
+    assert re.search(r"insv2v_abi_version\(void\) \{ return 15; \}", src)
     assert "insv2v_maskstep_desc must begin with the fields of insv2v_mstep_desc" in src   # the static_assert
     # the descriptor: insv2v_mstep_desc's fields in their order, then the known region
     kind = {p: "p", i64: "q", i32: "i", f32: "f"}

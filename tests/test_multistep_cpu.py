@@ -185,9 +185,9 @@ def test_interfaces():
     from insv2v.schedulers import DPMSolverMultistepScheduler
     header = open(os.path.join(ROOT, "include", "insv2v_hip.h")).read()
     assert re.search(r"^int insv2v_cfg_step_ms\(const insv2v_mstep_desc\* d, insv2v_stream_t stream\);", header, flags=re.M)
-    assert _lib.ABI_VERSION == 14
+    assert _lib.ABI_VERSION == 15
     src = open(os.path.join(ROOT, "instruct-video-to-video_amd", "csrc", "elementwise.hip")).read()
-    assert re.search(r"insv2v_abi_version\(void\) \{ return 14; \}", src)
+    assert re.search(r"insv2v_abi_version\(void\) \{ return 15; \}", src)
     step = [("eps_in", "p"), ("latent", "p"), ("latent_ref", "p"), ("delta_q", "p"), ("noise", "p"), ("rescale_stats", "p"),
             ("latent_out", "p"), ("pred_x0", "p"), ("eps_out", "p"), ("nbranch", "i"), ("F", "i"), ("h", "i"), ("w", "i"), ("R", "i"),
             ("correct", "i"), ("text_cfg", "f"), ("img_cfg", "f"), ("sqrt_a", "f"), ("sqrt_1ma", "f"), ("c_x0", "f"), ("c_eps", "f"),

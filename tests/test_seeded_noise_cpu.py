@@ -72,11 +72,11 @@ def test_stream_ids_do_not_depend_on_the_world_size():
     assert reachable(1) == reachable(2) == reachable(3) and len(reachable(1)) == 7
 
 
-def test_header_and_ctypes_mirror_carry_abi_14():
+def test_header_and_ctypes_mirror_carry_abi_15():
     import ctypes
     from insv2v import _lib
     header = open(ROOT + "/include/insv2v_hip.h").read()
-    assert _lib.ABI_VERSION == 14
+    assert _lib.ABI_VERSION == 15
     for name in ("insv2v_randn", "insv2v_posterior_sample_seeded"):
         assert re.search(r"^int %s\(" % name, header, flags=re.M), name
         assert name in _lib.SIGNATURES
