@@ -50,7 +50,8 @@ typedef void* insv2v_stream_t; /* hipStream_t */
 /* ABI version, bumped on any struct change.
  * ABI 14: seeded noise - insv2v_randn, insv2v_posterior_sample_seeded and the noise_seed / noise_stream / noise_on fields of
  * insv2v_step_desc (section "seeded noise" below holds the stream definition, which is part of this contract).
- * ABI 15: insv2v_groupnorm_plan (an addition: no existing struct or entry changes). */
+ * ABI 15: insv2v_groupnorm_plan (an addition: no existing struct or entry changes); likewise the CLIP scoring entries
+ * (insv2v_clip_preprocess, insv2v_clip_scores, insv2v_l2_normalize), added without a bump. */
 int insv2v_abi_version(void);
 /* One-time per-process setup (kernel attributes). Safe to call repeatedly. */
 int insv2v_init(void);
@@ -789,6 +790,41 @@ int insv2v_raft_flow_rows(float* coords1, const float* delta, int64_t ldd, void*
  * 576 logits per pixel (fp16 rows, k * 64 + i * 8 + j) -> fp32 [B, 2, 8h, 8w] */
 int insv2v_convex_upsample(const float* coords1, const void* mask, int64_t ldm, float* out, int32_t B, int32_t h, int32_t w,
                            insv2v_stream_t stream);
+
+/*
+ * ---- scoring an edit with CLIP (additions to ABI 15: no existing struct or entry changes) -----------------------------------------------
+ * The kernels behind ClipSimilarity (misc_utils/clip_similarity.py:10-47) that are not insv2v_gemm / insv2v_layernorm / insv2v_attention.
+ */
+typedef struct insv2v_clip_preprocess_desc {
+    const void* x;        /* frames [n, 3, H, W], fp16 or fp32 (x_fp32), element strides below: any view of a larger tensor */
+    void* out;            /* fp16 [n * (S/P)^2, ld]: patch rows in (frame, patch row, patch column) order, column c*P*P + py*P + px - the
+                           * flattened patch_embedding.weight [C, 3, P, P] order; columns [3*P*P, ld) are written as exact zeros */
+    int64_t stride_n, stride_c, stride_h, stride_w;
+    int64_t ld;
+    int32_t n, H, W, S, P, x_fp32;
+    float in_scale, in_shift;   /* pixel = in_scale * x + in_shift maps the frames to [0, 1] (0.5, 0.5 for frames in [-1, 1]) */
+    float mean[3], std[3];      /* per channel: (pixel - mean) / std */
+} insv2v_clip_preprocess_desc;
+/* encode_image's pixel front end (:29-31) in one pass, no intermediate image: F.interpolate(size = (S, S), mode = "bicubic",
+ * align_corners = False) - source coordinate (dst + 0.5) * in / out - 0.5 NOT clamped, cubic convolution with A = -0.75, the 4 x 4 tap
+ * indices clamped to the border, no antialias, the overshoot of the cubic NOT clamped - then (pixel - mean_c) / std_c; fp32 arithmetic,
+ * one fp16 rounding of the stored value.  S x S is square whatever the frame's aspect, as in the reference.
+ * INSV2V_EINVAL: S % P != 0, ld < 3*P*P, n / H / W / S / P <= 0, a std that is not positive, x or out NULL. */
+int insv2v_clip_preprocess(const insv2v_clip_preprocess_desc* d, insv2v_stream_t stream);
+/* The metrics of frame i from the towers' features: img0 / img1 [n, D] (row strides ld0 / ld1 elements), txt0 / txt1 [D] for every frame
+ * (ldt = 0) or [n, D] (row stride ldt); all four fp16, or all four fp32 (fp32 != 0).  Every operand is L2-normalised first (:25, :33: no
+ * eps), then out[i] (fp32 [n, 5]) =
+ *   sim_0 = cos(img0, txt0), sim_1 = cos(img1, txt1), sim_direction = cos(img1 - img0, txt1 - txt0), sim_image = cos(img0, img1),
+ *   consistency = cos(img1[i], img1[i + 1]) with the last frame's entry exact 0,
+ * where cos(x, y) = sum(x / max(|x|, eps) * y / max(|y|, eps)) is F.cosine_similarity (each norm clamped on its own; eps 1e-8 there).
+ * fp32 sums in a fixed order: two calls give the same bits.  INSV2V_EINVAL: n or D <= 0, a row stride below D (ldt: other than 0),
+ * eps <= 0, a NULL pointer. */
+int insv2v_clip_scores(const void* img0, const void* img1, const void* txt0, const void* txt1, int32_t fp32, int64_t ld0, int64_t ld1,
+                       int64_t ldt, int32_t n, int32_t D, float eps, float* out, insv2v_stream_t stream);
+/* out[i] (fp32, row stride ldo) = x[i] / |x[i]| for the n rows of x [n, D] (fp16, or fp32 with fp32 != 0; row stride ldx): the last line
+ * of encode_image / encode_text (:25, :33; no eps, as there).  out may be x when x is fp32.  INSV2V_EINVAL: n or D <= 0, a row stride
+ * below D, a NULL pointer. */
+int insv2v_l2_normalize(const void* x, int32_t fp32, int64_t ldx, float* out, int64_t ldo, int32_t n, int32_t D, insv2v_stream_t stream);
 
 #ifdef __cplusplus
 }

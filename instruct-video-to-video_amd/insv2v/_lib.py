@@ -129,6 +129,12 @@ class CorrLookupDesc(C.Structure):
                 ("B", c_i32), ("h", c_i32), ("w", c_i32), ("levels", c_i32), ("radius", c_i32)]
 
 
+class ClipPreprocessDesc(C.Structure):
+    _fields_ = [("x", c_p), ("out", c_p), ("stride_n", c_i64), ("stride_c", c_i64), ("stride_h", c_i64), ("stride_w", c_i64), ("ld", c_i64),
+                ("n", c_i32), ("H", c_i32), ("W", c_i32), ("S", c_i32), ("P", c_i32), ("x_fp32", c_i32),
+                ("in_scale", c_f32), ("in_shift", c_f32), ("mean", c_f32 * 3), ("std", c_f32 * 3)]
+
+
 # name -> (restype, argtypes); mirrors include/insv2v_hip.h one to one.
 SIGNATURES = {
     "insv2v_abi_version": (c_i32, []),
@@ -185,6 +191,9 @@ SIGNATURES = {
     "insv2v_corr_lookup": (c_i32, [C.POINTER(CorrLookupDesc), c_p]),
     "insv2v_raft_flow_rows": (c_i32, [c_p, c_p, c_i64, c_p, c_i64, c_i32, c_i32, c_i32, c_i32, c_p]),
     "insv2v_convex_upsample": (c_i32, [c_p, c_p, c_i64, c_p, c_i32, c_i32, c_i32, c_p]),
+    "insv2v_clip_preprocess": (c_i32, [C.POINTER(ClipPreprocessDesc), c_p]),
+    "insv2v_clip_scores": (c_i32, [c_p, c_p, c_p, c_p, c_i32, c_i64, c_i64, c_i64, c_i32, c_i32, c_f32, c_p, c_p]),
+    "insv2v_l2_normalize": (c_i32, [c_p, c_i32, c_i64, c_p, c_i64, c_i32, c_i32, c_p]),
 }
 
 _lib = None

@@ -1019,3 +1019,77 @@ def convex_upsample(coords1, mask, B, h, w):
     check(lib.insv2v_convex_upsample(coords1.data_ptr(), mask.data_ptr(), mask.stride(0), out.data_ptr(), B, h, w, _stream()),
           "insv2v_convex_upsample")
     return out
+
+
+# ----------------------------------------------------------------------------- scoring an edit with CLIP (insv2v/clip_score.py)
+CLIP_MEAN = (0.48145466, 0.4578275, 0.40821073)   # clip_similarity.py:19-20
+CLIP_STD = (0.26862954, 0.26130258, 0.27577711)
+
+
+def clip_preprocess(frames, size, patch, ld=None, in_scale=1.0, in_shift=0.0, mean=CLIP_MEAN, std=CLIP_STD, out=None):
+    """frames [n,3,H,W] fp16 / fp32 (any strided view) -> fp16 patch rows [n * (size/patch)^2, ld] of the bicubic-resized, mean / std
+    normalised size x size image (insv2v_clip_preprocess); ld defaults to 3 * patch^2 rounded up to 64, pad columns are zeros."""
+    lib = _lib.load()
+    if not torch.is_tensor(frames) or not frames.is_cuda or frames.dtype not in (torch.float16, torch.float32):
+        raise _lib.HipKernelError("clip_preprocess.frames: expected a CUDA float16 / float32 tensor")
+    if frames.dim() != 4 or frames.shape[1] != 3:
+        raise _lib.HipKernelError(f"clip_preprocess: frames {tuple(frames.shape)} must be [n,3,H,W]")
+    n, _, H, W = frames.shape
+    if ld is None:
+        ld = -(-3 * patch * patch // 64) * 64
+    g = size // patch if patch > 0 else 0
+    if out is None:
+        out = torch.empty((max(n * g * g, 0), max(ld, 0)), device=frames.device, dtype=torch.float16)
+    else:
+        _req(out, torch.float16, "clip_preprocess.out")
+        if out.dim() != 2 or out.stride(1) != 1 or out.stride(0) != ld or out.shape[0] < n * g * g or out.shape[1] < min(ld, 3 * patch * patch):
+            raise _lib.HipKernelError(f"clip_preprocess: out {tuple(out.shape)} (row stride {out.stride(0)}) does not hold {n * g * g} rows of ld {ld}")
+    d = _lib.ClipPreprocessDesc()
+    d.x, d.out, d.ld = frames.data_ptr() or None, out.data_ptr() or None, ld
+    d.stride_n, d.stride_c, d.stride_h, d.stride_w = frames.stride()
+    d.n, d.H, d.W, d.S, d.P, d.x_fp32 = n, H, W, size, patch, int(frames.dtype == torch.float32)
+    d.in_scale, d.in_shift = in_scale, in_shift
+    d.mean[:], d.std[:] = [float(v) for v in mean], [float(v) for v in std]
+    with _timed("elementwise", 0.0, ("clip_pre", n, H, W, size)):
+        check(lib.insv2v_clip_preprocess(_byref(d), _stream()), "insv2v_clip_preprocess")
+    return out
+
+
+def clip_scores(img0, img1, txt0, txt1, eps=1e-8):
+    """Features img0 / img1 [n, D] and txt0 / txt1 [D] (one prompt for every frame) or [n, D], all float16 or all float32 ->
+    fp32 [n, 5] = (sim_0, sim_1, sim_direction, sim_image, consistency) per frame (insv2v_clip_scores)."""
+    lib = _lib.load()
+    dt = img0.dtype if torch.is_tensor(img0) else None
+    if dt not in (torch.float16, torch.float32):
+        raise _lib.HipKernelError("clip_scores: features must be CUDA float16 or float32 tensors")
+    for name, t in (("img0", img0), ("img1", img1), ("txt0", txt0), ("txt1", txt1)):
+        _req(t, dt, "clip_scores." + name)
+        if t.stride(-1) != 1:
+            raise _lib.HipKernelError(f"clip_scores: {name} rows must be contiguous")
+    if img0.dim() != 2 or img1.shape != img0.shape:
+        raise _lib.HipKernelError(f"clip_scores: img0 {tuple(img0.shape)} and img1 {tuple(img1.shape)} must both be [n, D]")
+    n, D = img0.shape
+    if txt0.shape != txt1.shape or tuple(txt0.shape) not in ((D,), (1, D), (n, D)):
+        raise _lib.HipKernelError(f"clip_scores: txt0 {tuple(txt0.shape)} / txt1 {tuple(txt1.shape)} must be [{D}] or [{n}, {D}]")
+    ldt = 0
+    if txt0.dim() == 2 and txt0.shape[0] == n and n > 1:
+        if txt0.stride(0) != txt1.stride(0):
+            txt1 = txt1.contiguous()
+            txt0 = txt0.contiguous()
+        ldt = txt0.stride(0)
+    out = torch.empty((n, 5), device=img0.device, dtype=torch.float32)
+    with _timed("elementwise", 0.0, ("clip_scores", n, D)):
+        check(lib.insv2v_clip_scores(img0.data_ptr(), img1.data_ptr(), txt0.data_ptr(), txt1.data_ptr(), int(dt == torch.float32),
+                                     img0.stride(0), img1.stride(0), ldt, n, D, eps, out.data_ptr(), _stream()), "insv2v_clip_scores")
+    return out
+
+
+def l2_normalize(x):
+    """x [n, D] float16 / float32 -> fp32 [n, D] = x / |x| per row (insv2v_l2_normalize)."""
+    lib = _lib.load()
+    if not torch.is_tensor(x) or not x.is_cuda or x.dtype not in (torch.float16, torch.float32) or x.dim() != 2 or x.stride(1) != 1:
+        raise _lib.HipKernelError("l2_normalize: expected a CUDA float16 / float32 [n, D] tensor with contiguous rows")
+    out = torch.empty(tuple(x.shape), device=x.device, dtype=torch.float32)
+    check(lib.insv2v_l2_normalize(x.data_ptr(), int(x.dtype == torch.float32), x.stride(0), out.data_ptr(), out.stride(0), x.shape[0],
+                                  x.shape[1], _stream()), "insv2v_l2_normalize")
+    return out

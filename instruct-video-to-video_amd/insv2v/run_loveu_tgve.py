@@ -8,6 +8,9 @@
 {"frames": [n,T,3,H,W], "text_cond": [n,77,768], "text_uncond": [1,77,768]}, or - as the reference - the LOVEU-TGVE
 dataset under ``--data-dir`` (``insv2v/video_io.py``: CSV + frames, prompts from ``--edit-prompt-file``, CLIP text tower on
 the HIP kernels with the BPE vocabulary from ``--tokenizer-dir``), writing the reference's GIF / JPG result tree.
+
+With ``--score-ckpt FILE --score-out FILE.json`` (or ``--score-synthetic`` next to ``--synthetic``) every unit is scored after its edit
+with CLIP on the HIP kernels (``insv2v/clip_score.py``: the reference's ``ClipSimilarity`` numbers, text alignment, frame consistency).
 """
 import argparse
 import os
@@ -320,6 +323,13 @@ def build_parser():
                    help="torchvision raft_large checkpoint (state dict) for --with_optical_flow: the estimator runs on the HIP kernels")
     p.add_argument("--flows", type=str, default=None,
                    help=".pt file with precomputed optical flows for --with_optical_flow: flows[unit][window][query] = [R,2,H,W]")
+    p.add_argument("--score-ckpt", type=str, default=None,
+                   help="CLIP checkpoint (state dict, transformers CLIPModel or OpenAI clip layout) to score every edit with: CLIP text "
+                        "alignment and frame consistency on the HIP kernels (insv2v/clip_score.py)")
+    p.add_argument("--score-name", type=str, default="ViT-L/14", help="the CLIP model --score-ckpt holds (the reference's ViT names)")
+    p.add_argument("--score-out", type=str, default=None, help="JSON file for the scores: one record per unit")
+    p.add_argument("--score-synthetic", action="store_true", help="with --synthetic: score with a key-hashed CLIP (no checkpoint needed)")
+    p.add_argument("--synthetic-tiny", action="store_true", help="with --synthetic: the reduced-width UNet / VAE (and scorer) configurations")
     return p
 
 
@@ -341,7 +351,45 @@ def check_args(args):
         raise SystemExit("--synthetic-mask needs --synthetic N (masks of real units come from the \"mask\" entry of a --units file)")
     if args.flows and args.units is None and not args.synthetic:
         raise SystemExit("--flows is supported with --units / --synthetic (flows are indexed by unit)")
+    score_synth, score_ckpt, score_out = (getattr(args, k, None) for k in ("score_synthetic", "score_ckpt", "score_out"))
+    if score_synth and not args.synthetic:
+        raise SystemExit("--score-synthetic needs --synthetic N (real units are scored with --score-ckpt FILE)")
+    if score_synth and score_ckpt:
+        raise SystemExit("--score-synthetic and --score-ckpt are two scorers: pass one")
+    if score_out and not (score_ckpt or score_synth):
+        raise SystemExit("--score-out needs a scorer: --score-ckpt FILE (or --score-synthetic with --synthetic N)")
+    if (score_ckpt or score_synth) and not score_out:
+        raise SystemExit("--score-ckpt / --score-synthetic need --score-out FILE.json for the scores")
+    if getattr(args, "synthetic_tiny", False) and not args.synthetic:
+        raise SystemExit("--synthetic-tiny needs --synthetic N")
     return args
+
+
+def build_scorer(args, device, tokenizer=None):
+    """The CLI's scorer (None without one): --score-ckpt in either layout, or key-hashed weights with --score-synthetic."""
+    from .clip_score import load_scorer, synthetic_scorer
+    if getattr(args, "score_synthetic", False):
+        return synthetic_scorer(device=device, tiny=getattr(args, "synthetic_tiny", False))
+    if getattr(args, "score_ckpt", None):
+        return load_scorer(args.score_ckpt, name=args.score_name, device=device, tokenizer=tokenizer)
+    return None
+
+
+def score_record(scorer, unit, frames, edited, source_text, edit_text):
+    """One record of --score-out: the unit id, the five per-frame lists and the two means (clip_score.ClipSimilarity.score_edit)."""
+    r = scorer.score_edit(frames, edited, source_text, edit_text)
+    return {"unit": int(unit), **{k: (v.tolist() if torch.is_tensor(v) else v) for k, v in r.items()}}
+
+
+def write_scores(path, records, rank=0, world=1):
+    """The records of this rank, sorted by unit id (with several ranks each writes its own FILE.rankR.json)."""
+    import json
+    if world > 1:
+        root, ext = os.path.splitext(path)
+        path = f"{root}.rank{rank}{ext}"
+    os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
+    with open(path, "w") as f:
+        json.dump(sorted(records, key=lambda r: r["unit"]), f, indent=1)
 
 
 def synthetic_mask(n, H, W):
@@ -361,11 +409,13 @@ def optical_flow_pipe_kwargs(args):
     return {"raft_state_dict": synth.synth_raft_state_dict(shapes.raft_shapes())}
 
 
-def run_dataset(args, model, pipe, rank=0, world=1):
+def run_dataset(args, model, pipe, rank=0, world=1, scorer=None):
     """The reference's main loop (insv2v_run_loveu_tgve.py:83-170): every (video, cfg, size) x 4 prompt kinds is one
     independent unit; units are dealt round-robin to ranks, each rank writes its own result files.  With ``--seed`` a unit's id is
     4 * (index of its (video, cfg, size) combination) + (index of its prompt kind): global, so it is the same on every rank and at every
-    world size; the conditioning latent the four prompts share is sampled from the ENC stream of the first of them."""
+    world size; the conditioning latent the four prompts share is sampled from the ENC stream of the first of them.
+    ``scorer`` (build_scorer): every unit is scored after its edit, the video's original caption as text_0 and the edit prompt as text_1,
+    and the records go to ``args.score_out``."""
     import json
     from .video_io import LoveuTgveVideoDataset, save_tensor_to_gif, save_tensor_to_images, output_paths
     if model.text_model is None or model.text_model.tokenizer is None:
@@ -374,6 +424,7 @@ def run_dataset(args, model, pipe, rank=0, world=1):
     combos = list(product(range(len(prompts)), args.text_cfg, args.video_cfg, args.num_frames, args.image_size))
     seed = getattr(args, "seed", None)
     kinds = ("style", "object", "background", "multiple")
+    records = []
     for ci, (video_id, text_cfg, video_cfg, num_frames, image_size) in enumerate(combos):
         if ci % world != rank:
             continue
@@ -393,15 +444,29 @@ def run_dataset(args, model, pipe, rank=0, world=1):
                 continue
             todo.append((gif_path, image_dir, dict(frames=frames, text_cond=model.encode_text([prompt]), text_uncond=text_uncond,
                                                    text_cfg=text_cfg, video_cfg=video_cfg, cond=cond, unit=4 * ci + kinds.index(key),
-                                                   strength=getattr(args, "strength", 1.0))))
+                                                   strength=getattr(args, "strength", 1.0)), prompt))
         # the four prompts of a video share the conditioning latent and the window plan: one stacked launch chain per window (B = 12)
         if getattr(args, "no_stack", False):
-            edits = [edit_videos(model, pipe, [u], seed=seed)[0] for _, _, u in todo]
+            edits = [edit_videos(model, pipe, [u], seed=seed)[0] for _, _, u, _ in todo]
         else:
-            edits = edit_videos(model, pipe, [u for _, _, u in todo], seed=seed, max_clips=getattr(args, "max_stack", None))
-        for (gif_path, image_dir, _), edited in zip(todo, edits):
+            edits = edit_videos(model, pipe, [u for _, _, u, _ in todo], seed=seed, max_clips=getattr(args, "max_stack", None))
+        for (gif_path, image_dir, u, prompt), edited in zip(todo, edits):
+            if scorer is not None:   # the edited frames are still on the device
+                records.append(score_record(scorer, u["unit"], frames, edited, batch["original"], prompt))
             save_tensor_to_gif(torch.cat([frames.float().cpu(), edited.float().cpu()], dim=4), gif_path, fps=5)
             save_tensor_to_images(edited.float().cpu(), image_dir)
+    if scorer is not None:
+        write_scores(args.score_out, records, rank, world)
+
+
+def _score_texts(data, i, scorer):
+    """(source prompt, edit prompt) of unit i of a --units / --synthetic run: the ``source_ids`` / ``edit_ids`` [n,77] token ids of the
+    file, else its ``source_text`` / ``edit_text`` strings (they need the tokenizer); synthetic runs hash their ids."""
+    if "source_ids" in data and "edit_ids" in data:
+        return data["source_ids"][i:i + 1], data["edit_ids"][i:i + 1]
+    if "source_text" in data and "edit_text" in data:
+        return data["source_text"][i], data["edit_text"][i]
+    raise SystemExit("scoring --units needs source_ids / edit_ids (token ids [n,77]) or source_text / edit_text in the file")
 
 
 def main(argv=None):
@@ -412,6 +477,7 @@ def main(argv=None):
     from .clip_parallel import shard_units, gather_frames
 
     args = check_args(build_parser().parse_args(argv))
+    tok = None
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -419,12 +485,12 @@ def main(argv=None):
     if world > 1:
         dist.init_process_group("nccl")
     if args.synthetic:
-        conf = {"unet": {"params": synth.UNET_FULL}, "vae": {"params": synth.VAE_FULL}}
+        ucfg, vcfg = (synth.UNET_TINY, synth.VAE_TINY) if args.synthetic_tiny else (synth.UNET_FULL, synth.VAE_FULL)
+        conf = {"unet": {"params": ucfg}, "vae": {"params": vcfg}}
         model = create_model(conf, device=f"cuda:{local}")
-        model.unet.load_state_dict(synth.synth_state_dict(shapes.unet_shapes(**synth.UNET_FULL)))
-        model.vae.load_state_dict(synth.synth_state_dict(shapes.vae_shapes(**synth.VAE_FULL)))
+        model.unet.load_state_dict(synth.synth_state_dict(shapes.unet_shapes(**ucfg)))
+        model.vae.load_state_dict(synth.synth_state_dict(shapes.vae_shapes(**vcfg)))
     else:
-        tok = None
         if args.tokenizer_dir:
             from transformers import CLIPTokenizer
             tok = CLIPTokenizer.from_pretrained(args.tokenizer_dir, local_files_only=True)
@@ -435,13 +501,18 @@ def main(argv=None):
         g = torch.Generator().manual_seed(0)
         T, S = args.num_frames[0], args.image_size[0]
         data = {"frames": torch.rand((args.synthetic, T, 3, S, S), generator=g) * 2 - 1,
-                "text_cond": torch.randn((args.synthetic, 77, 768), generator=g),
-                "text_uncond": torch.randn((1, 77, 768), generator=g)}
+                "text_cond": torch.randn((args.synthetic, 77, ucfg["cross_attention_dim"]), generator=g),
+                "text_uncond": torch.randn((1, 77, ucfg["cross_attention_dim"]), generator=g)}
         if args.synthetic_mask:
             data["mask"] = synthetic_mask(args.synthetic, S, S)
+        if args.score_synthetic:   # no captions in a synthetic run: hashed token ids stand in for the source and the edit prompt
+            vocab = (synth.CLIP_TINY if args.synthetic_tiny else synth.CLIP_FULL)["vocab_size"]
+            data["source_ids"] = synth.synth_token_ids("score.source", args.synthetic, 77, vocab)
+            data["edit_ids"] = synth.synth_token_ids("score.edit", args.synthetic, 77, vocab)
     elif args.units is None:
         cls = InferenceIP2PVideoOpticalFlow if args.with_optical_flow else InferenceIP2PVideo
-        run_dataset(args, model, cls(unet=model.unet, num_ddim_steps=args.steps, scheduler=args.scheduler, solver_order=args.solver_order, **optical_flow_pipe_kwargs(args)), rank, world)
+        run_dataset(args, model, cls(unet=model.unet, num_ddim_steps=args.steps, scheduler=args.scheduler, solver_order=args.solver_order, **optical_flow_pipe_kwargs(args)), rank, world,
+                    scorer=build_scorer(args, f"cuda:{local}", tok))
         if world > 1:
             dist.destroy_process_group()
         return
@@ -454,6 +525,8 @@ def main(argv=None):
     item_shape = tuple(data["frames"].shape[1:])  # a rank without units still takes part in the all_gather
     masks = data.get("mask")   # optional [n,T,H,W] / [n,1,H,W]
     edit = lambda i: dict(mask=masks[i:i + 1] if masks is not None else None, strength=args.strength, mask_mode=args.mask_mode)
+    scorer = build_scorer(args, f"cuda:{local}", tok)
+    records = []
     outs = []
     for ci, (text_cfg, video_cfg) in enumerate(product(args.text_cfg, args.video_cfg)):
         mine = shard_units(n, rank, world)
@@ -473,8 +546,12 @@ def main(argv=None):
                                                             text_uncond=data["text_uncond"], text_cfg=text_cfg, video_cfg=video_cfg, unit=ci * n + i, **edit(i),
                                                             **({"flows_per_window": flows[i]} if flows is not None else {}))
                                                        for i in mine[g:g + cap]], seed=args.seed, max_clips=args.max_stack)
+        for i, edited in zip(mine, local_out if scorer is not None else []):
+            records.append(score_record(scorer, ci * n + i, data["frames"][i:i + 1], edited, *_score_texts(data, i, scorer)))
         local_out = torch.cat(local_out, 0).half() if local_out else torch.zeros((0, *item_shape), device=model.unet.device).half()
         outs.append(gather_frames(local_out, n, item_shape=item_shape))
+    if scorer is not None:
+        write_scores(args.score_out, records, rank, world)
     if rank == 0:
         os.makedirs(os.path.dirname(args.out) or ".", exist_ok=True)
         torch.save(torch.stack(outs, 0).cpu(), args.out)

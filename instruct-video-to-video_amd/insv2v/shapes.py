@@ -166,9 +166,13 @@ def vae_shapes(ddconfig, embed_dim=4, **unused):
 
 
 def clip_text_shapes(vocab_size=49408, hidden_size=768, intermediate_size=3072, num_hidden_layers=12,
-                     max_position_embeddings=77, prefix="transformer.text_model.", **unused):
-    """FrozenCLIPEmbedder state dict as stored in the reference checkpoint (``text_model.`` + these keys)."""
+                     max_position_embeddings=77, prefix="transformer.text_model.", projection_dim=None, with_projection=False, **unused):
+    """FrozenCLIPEmbedder state dict as stored in the reference checkpoint (``text_model.`` + these keys).
+    ``with_projection`` (with the config's ``projection_dim``): also ``text_projection.weight`` of transformers
+    ``CLIPTextModelWithProjection`` (no prefix: it sits next to ``text_model.``)."""
     d = {}
+    if with_projection:
+        d["text_projection.weight"] = (projection_dim, hidden_size)
     C = hidden_size
     d[prefix + "embeddings.token_embedding.weight"] = (vocab_size, C)
     d[prefix + "embeddings.position_embedding.weight"] = (max_position_embeddings, C)
@@ -181,6 +185,28 @@ def clip_text_shapes(vocab_size=49408, hidden_size=768, intermediate_size=3072, 
         _lin(d, f"{k}.mlp.fc2", C, intermediate_size)
         _norm(d, f"{k}.layer_norm2", C)
     _norm(d, prefix + "final_layer_norm", C)
+    return d
+
+
+def clip_vision_shapes(hidden_size=1024, intermediate_size=4096, num_hidden_layers=24, image_size=224, patch_size=14,
+                       projection_dim=768, **unused):
+    """transformers ``CLIPVisionModelWithProjection`` state dict (``vision_model.*`` + ``visual_projection.weight``): key -> shape."""
+    d = {}
+    C, v = hidden_size, "vision_model."
+    d[v + "embeddings.class_embedding"] = (C,)
+    d[v + "embeddings.patch_embedding.weight"] = (C, 3, patch_size, patch_size)
+    d[v + "embeddings.position_embedding.weight"] = ((image_size // patch_size) ** 2 + 1, C)
+    _norm(d, v + "pre_layrnorm", C)   # (transformers' own spelling)
+    for i in range(num_hidden_layers):
+        k = f"{v}encoder.layers.{i}"
+        for n in ("q_proj", "k_proj", "v_proj", "out_proj"):
+            _lin(d, f"{k}.self_attn.{n}", C, C)
+        _norm(d, f"{k}.layer_norm1", C)
+        _lin(d, f"{k}.mlp.fc1", intermediate_size, C)
+        _lin(d, f"{k}.mlp.fc2", C, intermediate_size)
+        _norm(d, f"{k}.layer_norm2", C)
+    _norm(d, v + "post_layernorm", C)
+    d["visual_projection.weight"] = (projection_dim, C)
     return d
 
 

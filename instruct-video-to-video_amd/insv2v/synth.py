@@ -34,7 +34,7 @@ def synth_tensor(key, ref, salt=0):
     if key.endswith("pos_encoder.pe"):
         return ref.clone().float() if hasattr(ref, "clone") else _pe_table(shape)
     is_norm = any(s in key for s in (".norm", "norm1.", "norm2.", "norm3.", "norms.", "ff_norm", "norm_out", "conv_norm_out", "layer_norm")) \
-        or key.startswith("norm")
+        or key.startswith("norm") or ".pre_layrnorm." in key or ".post_layernorm." in key   # (the CLIP image tower's two; no older key has them)
     if key.endswith("num_batches_tracked"):
         return torch.zeros(shape, dtype=torch.long)
     if key.endswith("running_var"):            # BatchNorm statistics (the optical-flow context encoder): positive
@@ -98,9 +98,14 @@ VAE_TINY = dict(embed_dim=4, ddconfig=dict(VAE_FULL["ddconfig"], ch=64, ch_mult=
 
 # CLIP ViT-L/14 text tower (openai/clip-vit-large-patch14, modules/openclip/modules.py:96) and a reduced-width variant
 CLIP_FULL = dict(vocab_size=49408, hidden_size=768, intermediate_size=3072, num_hidden_layers=12, num_attention_heads=12,
-                 max_position_embeddings=77)
+                 max_position_embeddings=77, projection_dim=768)
 CLIP_TINY = dict(vocab_size=1000, hidden_size=64, intermediate_size=128, num_hidden_layers=2, num_attention_heads=4,
-                 max_position_embeddings=77)
+                 max_position_embeddings=77, projection_dim=32)
+# CLIP ViT-L/14 image tower (the model behind ClipSimilarity, misc_utils/clip_similarity.py:11-16) and a reduced-width variant
+CLIP_VISION_FULL = dict(hidden_size=1024, intermediate_size=4096, num_hidden_layers=24, num_attention_heads=16, image_size=224,
+                        patch_size=14, projection_dim=768)
+CLIP_VISION_TINY = dict(hidden_size=64, intermediate_size=128, num_hidden_layers=2, num_attention_heads=4, image_size=28,
+                        patch_size=14, projection_dim=32)
 
 
 def synth_token_ids(name, n, L, vocab, salt=0):
