@@ -474,8 +474,11 @@ int insv2v_layernorm_stats(const void* x, float* stats, int64_t ldx, int32_t row
  * head_dim is one of 16, 32, 40, 64, 80, 128, 160 or 512 (INSV2V_EUNSUPPORTED for another multiple of 8 up to 160, INSV2V_EINVAL for
  * anything else); seq_q, seq_k >= 1.
  * head_dim = 512 (the VAE's one-head mid AttnBlock, modules/vqvae/model.py:145-197): plain softmax only - causal != 0 or bias tables
- * return INSV2V_EUNSUPPORTED; any seq_q / seq_k / batch / heads; one problem's K and V rows have to lie within 2 GiB of its base
- * (seq_k * max(k_rs, v_rs) * 2 bytes; INSV2V_EUNSUPPORTED beyond), the per-problem bases themselves are 64-bit.
+ * return INSV2V_EUNSUPPORTED; any seq_q / seq_k / batch / heads.
+ * Every head_dim: one problem's K and V rows have to lie within 2 GiB of its (problem, head) base, because the kernels load them
+ * through one buffer descriptor with 32-bit byte offsets: (seq_k * max(k_rs, v_rs) + head_dim) * 2 > 0x7fffffff bytes returns
+ * INSV2V_EUNSUPPORTED (the <= 16-row kernel loads only V that way: its rule is on v_rs alone).  The per-problem bases themselves are
+ * 64-bit.  The row stride of temporal attention is h*w*ld, so a frame size alone can reach this.
  */
 typedef struct insv2v_attention_desc {
     const void* q;
@@ -499,6 +502,36 @@ typedef struct insv2v_attention_desc {
     int64_t bias_rs;
 } insv2v_attention_desc;
 int insv2v_attention(const insv2v_attention_desc* d, insv2v_stream_t stream);
+/* What insv2v_attention does with a descriptor, without doing it: the answer of the one planner (csrc/attn_plan.h) that insv2v_attention
+ * consults before it launches.  A pure function of the descriptor's integers, the null and alignment bits of its pointers, the CU count
+ * and the five A/B switches INSV2V_ATTN_SHORT / _FOLD / _SINGLE / _REP / _SHORT_WGS (read once per process); it touches no GPU.  A purely
+ * additive entry of ABI 15: no existing struct or entry changes. */
+#define INSV2V_ATTN_PLAN_NONE 0        /* refused (rc != 0) */
+#define INSV2V_ATTN_PLAN_SHORT 1       /* attn_short_kernel<d>: <= 16 queries and keys, one workgroup per problem, one wave per head */
+#define INSV2V_ATTN_PLAN_SHORT_BIAS 2  /* attn_short_kernel<d, true>: with the q / k / v bias tables, persistent over problems */
+#define INSV2V_ATTN_PLAN_GENERIC 3     /* attn_kernel<d, nw, kvt, qb, fold>: double-buffered key tiles */
+#define INSV2V_ATTN_PLAN_SINGLE 4      /* attn_kernel<160, 6, 96, 1, false, true>: the whole key sequence as one tile */
+#define INSV2V_ATTN_PLAN_SINGLE_REP 5  /* ... one workgroup serving the kv_inner consecutive problems that share one K / V */
+#define INSV2V_ATTN_PLAN_D512 6        /* attn_kernel<512, 4, 32, 1> */
+typedef struct insv2v_attention_plan_t {
+    int32_t rc;           /* 0, or what insv2v_attention returns without launching anything (INSV2V_EINVAL / INSV2V_EUNSUPPORTED) */
+    int32_t family;       /* INSV2V_ATTN_PLAN_* */
+    int32_t d;            /* template parameters: head dim, */
+    int32_t nw;           /*   waves per workgroup (SHORT: = heads), */
+    int32_t qb;           /*   16-row query blocks per wave, */
+    int32_t kvt;          /*   keys per tile (SHORT: 16), */
+    int32_t fold;         /*   the folded softmax (d = 40 / 80 with nw >= 4) */
+    int32_t threads;      /* threads per workgroup */
+    int32_t grid;         /* workgroups */
+    int32_t lds_bytes;    /* dynamic LDS per workgroup */
+    int32_t rows_per_wg;  /* query rows (over heads and problems) one workgroup serves: 16 nw qb; SINGLE_REP x kv_inner; SHORT 16 heads x the
+                           * problems a persistent workgroup takes.  rows_per_wg * grid >= seq_q * heads * batch */
+    int32_t ntiles;       /* key tiles per problem */
+    int32_t ragged;       /* != 0: the last tile holds fewer than kvt keys (the masking path runs) */
+} insv2v_attention_plan_t;
+/* cus <= 0: this device's CU count (0 without a GPU: the persistent short kernel is then planned with one workgroup per problem).
+ * Returns INSV2V_EINVAL for a NULL argument, else 0 with *out filled - also when out->rc says the problem is refused. */
+int insv2v_attention_plan(const insv2v_attention_desc* d, int32_t cus, insv2v_attention_plan_t* out);
 
 /*
  * Token + position embedding of the CLIP text encoder (transformers CLIPTextEmbeddings, called from

@@ -17,6 +17,7 @@
 // issued before the MFMAs of tile t.  Key masking is only executed on the ragged last tile (every tile when causal).
 #include "common.h"
 #include "gemm_dma.h"
+#include "attn_plan.h"
 #include <cstdlib>
 #include <algorithm>
 
@@ -97,6 +98,8 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 && D == 40) ? 4 : SINGLE ? 3 : (D
     // 16-byte output stores (see the P.V loop): 350 -> 322 us for the 96-token self-attention launch of the B = 60 stack; the REP form loses
     // 5 % with them (same-box A/B, profiles/r06_attn_rep.txt) and keeps the 8-byte ones
     constexpr bool ST16 = SINGLE && !REP && ATTN_SINGLE_ST16 && (DTA % 2 == 0) && (D % 32 == 0);
+    static_assert(!ST16 || sizeof(half8) == ATTN_SINGLE_O_ALIGN, "attn_plan.h restates the alignment the 16-byte output stores need");
+    static_assert(!SINGLE || KVT == ATTN_SINGLE_KVT, "attn_plan.h restates the single tile");
     constexpr int NCBF = D / 16;                  // full 16-channel blocks
     constexpr bool VHALF = (D % 16) != 0;        // + one 8-channel block
     constexpr int VIMG = NCBF * KVT * 32 + (VHALF ? KVT * 16 : 0);   // bytes of one V tile image
@@ -119,6 +122,8 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 && D == 40) ? 4 : SINGLE ? 3 : (D
     extern __shared__ __attribute__((aligned(16))) char smem[];
     half_t* sK = (half_t*)smem;                // [2][KVT][KLD]
     half_t* sVt = sK + NBUF * KVT * KLD;       // [NBUF][DP][VT_LD]
+    static_assert(DP == attn_dp(D) && (int64_t)NBUF * (KVT * (DP + 8) + DP * VT_LD) * sizeof(half_t) == attn_lds_bytes(D, KVT, SINGLE), "attn_plan.h restates the LDS");
+    static_assert(KLD <= DP + 8 && (!VDMA || 2 * VIMG + 16 <= NBUF * DP * VT_LD * (int)sizeof(half_t)), "the K rows and the V image fit the planned LDS");
 
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int g = lane >> 4, qc = lane & 15;
@@ -549,15 +554,15 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 && D == 40) ? 4 : SINGLE ? 3 : (D
 //   * only V goes through LDS, transposed ([d][16 keys], 40-byte rows), in a per-wave slice: no workgroup barrier;
 //   * all 8 heads of a token row are read by the same workgroup at the same time (full 128-byte lines from L1/L2).
 // 1.6-6.4 KB of LDS and ~48 VGPRs per wave: 32 waves per CU.
-#ifndef ATTN_SHORT_MAXT
-#define ATTN_SHORT_MAXT 512
-#endif
 template <int D, bool BIAS = false>
 __global__ __launch_bounds__(BIAS ? ATTN_SHORT_MAXT : 1024) void attn_short_kernel(insv2v_attention_desc p) {
     constexpr int KS = (D + 31) / 32;        // k steps of the QK^T contraction (head dim zero-padded in registers)
     constexpr int DT = (D + 15) / 16;        // 16-wide output column tiles
     constexpr int KCH = D / 8;               // 16-byte chunks per row
     constexpr int VT_LD = 20;                // halfs per transposed V row: 16 keys + 4 pad (40 B: conflict-free 8-byte reads)
+    static_assert(VT_LD == ATTN_SHORT_VT_LD && ATTN_SHORT_ROWS == 16, "attn_plan.h restates the V^T slice");
+    static_assert(ATTN_SHORT_MAXT % 64 == 0 && ATTN_SHORT_MAXT <= 1024 && ATTN_SHORT_MAX_HEADS * 64 <= 1024, "one wave per head inside the launch bounds");
+    static_assert(attn_short_lds_bytes(1, D) == DT * 16 * VT_LD * sizeof(half_t), "attn_plan.h restates the LDS per head");
     constexpr int V_ITERS = (8 * KCH + 63) / 64;  // (key pair, chunk) items per lane
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lane = threadIdx.x & 63, head = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // wave-uniform: scalar base pointers
@@ -687,46 +692,35 @@ __global__ __launch_bounds__(BIAS ? ATTN_SHORT_MAXT : 1024) void attn_short_kern
   }
 }
 
+// ------------------------------------------------------------------------------------------------------------
+// Launches.  What runs is decided by plan_attention (attn_plan.h) alone; the code below maps its answer to the template instantiation.
 template <int D>
-static int launch_short(const insv2v_attention_desc& d, hipStream_t s) {
-    constexpr int DT = (D + 15) / 16;
-    const size_t lds = (size_t)d.heads * DT * 16 * 20 * sizeof(half_t);
-    if (lds > 64 * 1024) return INSV2V_EUNSUPPORTED;  // beyond the default dynamic-LDS limit: the caller falls back to attn_kernel
-    if (d.q_bias && d.heads * 64 > ATTN_SHORT_MAXT) return INSV2V_EUNSUPPORTED;   // the biased form is compiled for <= 8 heads (its register budget)
-    // persistent over problems (see the kernel: the bias fragments are read once per wave): a few workgroups per CU, problems dealt round-robin
-    // so that workgroups running side by side read neighbouring token rows.  INSV2V_ATTN_SHORT_WGS = workgroups per CU (0: one per problem).
-    static const int wgs_per_cu = getenv("INSV2V_ATTN_SHORT_WGS") ? atoi(getenv("INSV2V_ATTN_SHORT_WGS")) : 2;
-    const int cus = insv2v_num_cus();
-    if (cus <= 0) return INSV2V_EINVAL;
-    const int grid = (wgs_per_cu > 0 && d.q_bias) ? (int)std::min<int64_t>(d.batch, (int64_t)cus * wgs_per_cu) : d.batch;
-    if (d.q_bias) hipLaunchKernelGGL((attn_short_kernel<D, true>), dim3(grid), dim3(d.heads * 64), lds, s, d);
-    else hipLaunchKernelGGL((attn_short_kernel<D>), dim3(grid), dim3(d.heads * 64), lds, s, d);
+static int launch_short(const insv2v_attention_desc& d, const insv2v_attention_plan_t& pl, hipStream_t s) {
+    if (pl.family == INSV2V_ATTN_PLAN_SHORT_BIAS) hipLaunchKernelGGL((attn_short_kernel<D, true>), dim3(pl.grid), dim3(pl.threads), pl.lds_bytes, s, d);
+    else hipLaunchKernelGGL((attn_short_kernel<D>), dim3(pl.grid), dim3(pl.threads), pl.lds_bytes, s, d);
     return launch_status();
 }
 
-static int dispatch_short(const insv2v_attention_desc& d, hipStream_t s) {
-    switch (d.head_dim) {
-        case 16: return launch_short<16>(d, s);
-        case 32: return launch_short<32>(d, s);
-        case 40: return launch_short<40>(d, s);
-        case 64: return launch_short<64>(d, s);
-        case 80: return launch_short<80>(d, s);
-        case 128: return launch_short<128>(d, s);
-        case 160: return launch_short<160>(d, s);
+static int dispatch_short(const insv2v_attention_desc& d, const insv2v_attention_plan_t& pl, hipStream_t s) {
+    switch (pl.d) {
+        case 16: return launch_short<16>(d, pl, s);
+        case 32: return launch_short<32>(d, pl, s);
+        case 40: return launch_short<40>(d, pl, s);
+        case 64: return launch_short<64>(d, pl, s);
+        case 80: return launch_short<80>(d, pl, s);
+        case 128: return launch_short<128>(d, pl, s);
+        case 160: return launch_short<160>(d, pl, s);
     }
-    return INSV2V_EUNSUPPORTED;
+    return INSV2V_EINVAL;   // (a plan this file has no kernel for)
 }
 
 template <int D, int NW, int QB, bool FOLD = false, int KVT_ = 0, bool SINGLE = false, bool REP = false>
-static int launch_attn(const insv2v_attention_desc& d, hipStream_t s) {
-    constexpr int DP = (D + 31) / 32 * 32;
-    constexpr int KVT = KVT_ ? KVT_ : (NW >= 4 ? 64 : 32);
-    constexpr size_t lds = (size_t)(SINGLE ? 1 : 2) * (KVT * (DP + 8) + DP * (KVT + 4)) * sizeof(half_t);
-    if constexpr (!FOLD && !SINGLE && (D == 40 || D == 80) && NW >= 4) {   // the folded softmax (INSV2V_ATTN_FOLD=0: the round-3 form, for A/B)
-        static const int fold = getenv("INSV2V_ATTN_FOLD") ? atoi(getenv("INSV2V_ATTN_FOLD")) : 1;
-        if (fold) return launch_attn<D, NW, QB, true>(d, s);
-    }
-    if (SINGLE && d.seq_k > KVT) return INSV2V_EUNSUPPORTED;
+static int launch_attn(const insv2v_attention_desc& d, const insv2v_attention_plan_t& pl, hipStream_t s) {
+    constexpr int KVT = KVT_ ? KVT_ : attn_kvt(NW);
+    constexpr size_t lds = (size_t)attn_lds_bytes(D, KVT, SINGLE);
+    static_assert(lds <= (size_t)ATTN_LDS_MAX, "more LDS than a CU has");
+    if (pl.d != D || pl.nw != NW || pl.qb != QB || pl.kvt != KVT || (pl.fold != 0) != FOLD || pl.threads != NW * 64 || pl.lds_bytes != (int)lds)
+        return INSV2V_EINVAL;   // (a plan this instantiation does not match)
     static bool attr_set = false;
     if (!attr_set) {
         hipError_t e = hipFuncSetAttribute((const void*)attn_kernel<D, NW, KVT, QB, FOLD, SINGLE, REP>,
@@ -734,77 +728,78 @@ static int launch_attn(const insv2v_attention_desc& d, hipStream_t s) {
         if (e != hipSuccess) return (int)e;
         attr_set = true;
     }
-    constexpr int rows = 16 * NW * QB;
-    if (REP && (d.kv_inner <= 1 || d.kv_step != 0 || d.batch % d.kv_inner)) return INSV2V_EUNSUPPORTED;
-    const int64_t nwg = (int64_t)((d.seq_q + rows - 1) / rows) * d.heads * (REP ? d.batch / d.kv_inner : d.batch);
-    if (nwg > 0x7fffffff) return INSV2V_EUNSUPPORTED;
-    hipLaunchKernelGGL((attn_kernel<D, NW, KVT, QB, FOLD, SINGLE, REP>), dim3((unsigned)nwg), dim3(NW * 64), lds, s, d);
+    hipLaunchKernelGGL((attn_kernel<D, NW, KVT, QB, FOLD, SINGLE, REP>), dim3((unsigned)pl.grid), dim3(NW * 64), lds, s, d);
     return launch_status();
+}
+
+// the folded softmax exists for the head dims with a spare contraction column, in the workgroups of 4 and 8 waves
+template <int D, int NW, int QB>
+static int launch_fold(const insv2v_attention_desc& d, const insv2v_attention_plan_t& pl, hipStream_t s) {
+    if constexpr ((D == 40 || D == 80) && NW >= 4) {
+        if (pl.fold) return launch_attn<D, NW, QB, true>(d, pl, s);
+    }
+    return launch_attn<D, NW, QB>(d, pl, s);
 }
 
 // Head dims of the path: 40/80/160 (UNet levels, 8 heads), 16/32/64/128 (reduced-width test configs).
 template <int NW, int QB>
-static int dispatch_dp(const insv2v_attention_desc& d, hipStream_t s) {
-    switch (d.head_dim) {
-        case 16: return launch_attn<16, NW, QB>(d, s);
-        case 32: return launch_attn<32, NW, QB>(d, s);
-        case 40: return launch_attn<40, NW, QB>(d, s);
-        case 64: return launch_attn<64, NW, QB>(d, s);
-        case 80: return launch_attn<80, NW, QB>(d, s);
-        case 128: return launch_attn<128, NW, QB>(d, s);
-        case 160: return launch_attn<160, NW, QB>(d, s);
+static int dispatch_dp(const insv2v_attention_desc& d, const insv2v_attention_plan_t& pl, hipStream_t s) {
+    switch (pl.d) {
+        case 16: return launch_fold<16, NW, QB>(d, pl, s);
+        case 32: return launch_fold<32, NW, QB>(d, pl, s);
+        case 40: return launch_fold<40, NW, QB>(d, pl, s);
+        case 64: return launch_fold<64, NW, QB>(d, pl, s);
+        case 80: return launch_fold<80, NW, QB>(d, pl, s);
+        case 128: return launch_fold<128, NW, QB>(d, pl, s);
+        case 160: return launch_fold<160, NW, QB>(d, pl, s);
     }
-    return INSV2V_EUNSUPPORTED;
+    return INSV2V_EINVAL;
+}
+
+// The A/B switches of the attention dispatch (attn_plan.h), read from the environment once for the library.
+static const attention_switches& insv2v_attention_switches() {
+    static const attention_switches sw = [] {
+        auto env = [](const char* name, int dflt) { const char* v = getenv(name); return v ? atoi(v) : dflt; };
+        attention_switches s;
+        s.short_on = env("INSV2V_ATTN_SHORT", s.short_on); s.fold = env("INSV2V_ATTN_FOLD", s.fold); s.single = env("INSV2V_ATTN_SINGLE", s.single);
+        s.rep = env("INSV2V_ATTN_REP", s.rep); s.short_wgs = env("INSV2V_ATTN_SHORT_WGS", s.short_wgs);
+        return s;
+    }();
+    return sw;
+}
+
+// ONE planner (attn_plan.h) answers for the launch and for the read-only entry, so that they cannot disagree
+extern "C" int insv2v_attention_plan(const insv2v_attention_desc* dp, int32_t cus, insv2v_attention_plan_t* out) {
+    if (!dp || !out) return INSV2V_EINVAL;
+    *out = plan_attention(*dp, insv2v_attention_switches(), cus > 0 ? cus : insv2v_num_cus());
+    return 0;
 }
 
 extern "C" int insv2v_attention(const insv2v_attention_desc* dp, insv2v_stream_t stream) {
     if (!one_device()) return INSV2V_EINVAL;
     if (!dp) return INSV2V_EINVAL;
     insv2v_attention_desc d = *dp;
-    if (!d.q || !d.k || !d.v || !d.o) return INSV2V_EINVAL;
-    if (d.head_dim <= 0 || (d.head_dim & 7) || (d.head_dim > 160 && d.head_dim != 512)) return INSV2V_EINVAL;
-    if (d.seq_q <= 0 || d.seq_k <= 0 || d.batch <= 0 || d.heads <= 0) return INSV2V_EINVAL;
-    if ((d.q_rs & 7) || (d.k_rs & 7) || (d.v_rs & 7) || (d.o_rs & 3)) return INSV2V_EINVAL;
-    if (d.q_inner <= 0) d.q_inner = 1;
+    const int cus = insv2v_num_cus();
+    const insv2v_attention_plan_t pl = plan_attention(d, insv2v_attention_switches(), cus);
+    if (pl.rc) return pl.rc;
+    if (d.q_inner <= 0) d.q_inner = 1;   // (the kernels divide by them)
     if (d.kv_inner <= 0) d.kv_inner = 1;
     if (d.o_inner <= 0) d.o_inner = 1;
     hipStream_t s = as_stream(stream);
-    // <= 16 queries and keys (temporal attention over the frames): one wave per head, no K tile in LDS
-    static const int short_on = getenv("INSV2V_ATTN_SHORT") ? atoi(getenv("INSV2V_ATTN_SHORT")) : 1;
-    const bool biased = d.q_bias || d.k_bias || d.v_bias;
-    if (biased && (!d.q_bias || !d.k_bias || !d.v_bias || (d.bias_rs & 7) || ((uintptr_t)d.q_bias & 15) || ((uintptr_t)d.k_bias & 15) || ((uintptr_t)d.v_bias & 15)))
-        return INSV2V_EINVAL;
-    // d = 512 (the VAE's one-head mid block): one form for every sequence length - four waves x 16 query rows over double-buffered 32-key
-    // tiles (137 KiB of LDS, one workgroup per CU, one wave per SIMD with O^T in 128 accumulator registers).  Plain softmax only.
-    if (d.head_dim == 512) {
-        if (d.causal || biased) return INSV2V_EUNSUPPORTED;
-        // the K / V tile loads are 32-bit byte offsets from the (problem, head) base
-        if (((int64_t)d.seq_k * std::max(d.k_rs, d.v_rs) + 512) * 2 > 0x7fffffffLL) return INSV2V_EUNSUPPORTED;
-        return launch_attn<512, 4, 1, false, 32>(d, s);
+    switch (pl.family) {
+        case INSV2V_ATTN_PLAN_SHORT_BIAS:
+            if (cus <= 0) return INSV2V_EINVAL;   // (the persistent grid is sized by the CU count)
+            return dispatch_short(d, pl, s);
+        case INSV2V_ATTN_PLAN_SHORT: return dispatch_short(d, pl, s);
+        case INSV2V_ATTN_PLAN_D512: return launch_attn<512, 4, 1, false, 32>(d, pl, s);
+        case INSV2V_ATTN_PLAN_SINGLE_REP: return launch_attn<160, 6, 1, false, 96, true, true>(d, pl, s);
+        case INSV2V_ATTN_PLAN_SINGLE: return launch_attn<160, 6, 1, false, 96, true>(d, pl, s);
+        case INSV2V_ATTN_PLAN_GENERIC:
+            if (pl.nw == 1 && pl.qb == 1) return dispatch_dp<1, 1>(d, pl, s);
+            if (pl.nw == 2 && pl.qb == 1) return dispatch_dp<2, 1>(d, pl, s);
+            if (pl.nw == 8 && pl.qb == 2) return dispatch_dp<8, 2>(d, pl, s);
+            if (pl.nw == 4 && pl.qb == 2) return dispatch_dp<4, 2>(d, pl, s);
+            if (pl.nw == 4 && pl.qb == 1) return dispatch_dp<4, 1>(d, pl, s);
     }
-    if ((short_on || biased) && d.seq_q <= 16 && d.seq_k <= 16 && !d.causal && d.heads <= 16) {
-        const int rc = dispatch_short(d, s);
-        if (rc != INSV2V_EUNSUPPORTED || biased) return rc;
-    }
-    if (biased) return INSV2V_EUNSUPPORTED;   // only the <= 16-row kernel adds the tables: never silently drop them
-    // 16 query rows per wave and query block: short query sequences (temporal, seq = frames) use
-    // 1-wave workgroups; long ones 4 waves x 2 query blocks = 128 rows per workgroup.
-    // the 96-token spatial self- / text cross-attention of the 8x12 level (d = 160): one workgroup of six waves per (frame, head), the
-    // whole key sequence as one 96-key tile in a single LDS buffer (two workgroups per CU) - the generic form below runs it as two
-    // half-filled 64-row workgroups with double-buffered 64-key tiles, one workgroup per CU (profiles/r04_attn_d160_single_tile.txt)
-    static const int single_on = getenv("INSV2V_ATTN_SINGLE") ? atoi(getenv("INSV2V_ATTN_SINGLE")) : 1;
-    // (three waves x two query blocks instead - every K / V fragment feeding two MFMAs - needs 256 VGPRs + spills and is slower: 401 vs 362 us)
-    // (its 16-byte output stores need 16-byte aligned output rows)
-    const bool o16 = !(d.o_rs & 7) && !((uintptr_t)d.o & 15) && !(d.o_outer & 7) && !(d.o_step & 7);
-    if (single_on && o16 && d.head_dim == 160 && !d.causal && d.seq_q > 64 && d.seq_q <= 96 && d.seq_k <= 96) {
-        // consecutive problems sharing one K / V (text cross-attention: the frames of a sample): one workgroup per (sample, head) keeps the tile
-        static const int rep_on = getenv("INSV2V_ATTN_REP") ? atoi(getenv("INSV2V_ATTN_REP")) : 1;
-        if (rep_on && d.kv_inner > 1 && d.kv_step == 0 && d.batch % d.kv_inner == 0) return launch_attn<160, 6, 1, false, 96, true, true>(d, s);
-        return launch_attn<160, 6, 1, false, 96, true>(d, s);
-    }
-    if (d.seq_q <= 16) return dispatch_dp<1, 1>(d, s);
-    if (d.seq_q <= 32) return dispatch_dp<2, 1>(d, s);
-    if (d.seq_q >= 512 && d.seq_q % 256 == 0 && d.head_dim <= 96) return dispatch_dp<8, 2>(d, s);
-    if (d.seq_q >= 128 && d.head_dim <= 96) return dispatch_dp<4, 2>(d, s);
-    return dispatch_dp<4, 1>(d, s);
+    return INSV2V_EINVAL;   // (a plan this file has no kernel for)
 }

@@ -99,6 +99,14 @@ class AttentionDesc(C.Structure):
                 ("scale", c_f32), ("causal", c_i32), ("q_bias", c_p), ("k_bias", c_p), ("v_bias", c_p), ("bias_rs", c_i64)]
 
 
+ATTN_PLAN_NONE, ATTN_PLAN_SHORT, ATTN_PLAN_SHORT_BIAS, ATTN_PLAN_GENERIC, ATTN_PLAN_SINGLE, ATTN_PLAN_SINGLE_REP, ATTN_PLAN_D512 = range(7)   # INSV2V_ATTN_PLAN_*
+
+
+class AttentionPlan(C.Structure):
+    """insv2v_attention_plan_t: what insv2v_attention does with a descriptor (insv2v_attention_plan; csrc/attn_plan.h)."""
+    _fields_ = [(n, c_i32) for n in ("rc", "family", "d", "nw", "qb", "kvt", "fold", "threads", "grid", "lds_bytes", "rows_per_wg", "ntiles", "ragged")]
+
+
 class StepDesc(C.Structure):
     _fields_ = [("eps_in", c_p), ("latent", c_p), ("latent_ref", c_p), ("delta_q", c_p), ("noise", c_p),
                 ("rescale_stats", c_p), ("latent_out", c_p), ("pred_x0", c_p), ("eps_out", c_p),
@@ -163,6 +171,7 @@ SIGNATURES = {
     "insv2v_layernorm": (c_i32, [C.POINTER(LayerNormDesc), c_p]),
     "insv2v_layernorm_stats": (c_i32, [c_p, c_p, c_i64, c_i32, c_i32, c_f32, c_p]),
     "insv2v_attention": (c_i32, [C.POINTER(AttentionDesc), c_p]),
+    "insv2v_attention_plan": (c_i32, [C.POINTER(AttentionDesc), c_i32, C.POINTER(AttentionPlan)]),
     "insv2v_embed_tokens": (c_i32, [c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_p]),
     "insv2v_softmax_rows": (c_i32, [c_p, c_p, c_i64, c_i64, c_i32, c_i32, c_f32, c_p]),
     "insv2v_softmax_rows_padded": (c_i32, [c_p, c_p, c_i64, c_i64, c_i32, c_i32, c_i32, c_f32, c_p]),

@@ -662,9 +662,21 @@ def attention(q_ptr, k_ptr, v_ptr, out, *, batch, heads, head_dim, seq_q, seq_k,
     return out
 
 
-def attention_short_supported(heads, head_dim, seq):
-    """True if insv2v_attention runs the one-wave-per-head kernel for this problem (the only one that takes qkv_bias)."""
-    return seq <= 16 and heads <= 16 and head_dim in (16, 32, 40, 64, 80, 128, 160) and heads * ((head_dim + 15) // 16) * 16 * 20 * 2 <= 64 * 1024
+def attention_short_supported(heads, head_dim, seq, biased=False):
+    """True if insv2v_attention runs the one-wave-per-head kernel for a temporal self-attention of `seq` frames (the only kernel that takes
+    qkv_bias); biased=True: with the bias tables.  The library's planner answers (insv2v_attention_plan): no rule is restated here."""
+    lib = _lib.load()
+    d, p = AttentionDesc(), _lib.AttentionPlan()
+    d.q = d.k = d.v = d.o = 16          # (the planner looks at null and alignment bits only)
+    if biased:
+        d.q_bias = d.k_bias = d.v_bias = 16
+        d.bias_rs = 3 * heads * head_dim
+    d.q_rs = d.k_rs = d.v_rs = 3 * heads * head_dim
+    d.o_rs = heads * head_dim
+    d.q_inner = d.kv_inner = d.o_inner = 1
+    d.batch, d.heads, d.head_dim, d.seq_q, d.seq_k, d.scale = 1, heads, head_dim, seq, seq, 1.0
+    check(lib.insv2v_attention_plan(_byref(d), 0, _byref(p)), "insv2v_attention_plan")
+    return p.rc == 0 and p.family in (_lib.ATTN_PLAN_SHORT, _lib.ATTN_PLAN_SHORT_BIAS)
 
 
 def embed_tokens(ids, tok, pos):

@@ -511,7 +511,7 @@ class MotionModule:
                     st = ops.layernorm_stats(h)                          # the q/k/v GEMM below folds the LayerNorm
                 if rl_frames:
                     qkv = ops.rowlin(h, self._qkv_stream(at, start, F), 3 * C, layernorm=True, frames=F, rows_per_frame=HW)
-                elif ATTN_PE_BIAS and ops.attention_short_supported(self.heads, hd, F):
+                elif ATTN_PE_BIAS and ops.attention_short_supported(self.heads, hd, F, biased=True):
                     pe_half = at["pe_half"].get((start, F))
                     if pe_half is None:
                         pe_half = at["pe_half"][(start, F)] = at["pe_bias"][start:start + F].half().contiguous()
