@@ -761,10 +761,12 @@ int insv2v_posterior_sample_seeded(const float* moments, float* z, int32_t N, in
  *               from u2, u3.  |z| <= 5.89.  The kernels evaluate this in fp32 from exact images of the words (csrc/rng.h); the error
  *               against a float64 evaluation is recorded in DESIGN.md.
  *   stream id   what the host packs per purpose (insv2v/rng.py stream_id(kind, unit, window, step)); the kernels take any int64_t:
- *                 bits 52-53 kind (0 ENC, 1 INIT, 2 STEP) | bits 28-51 unit (< 2^24) | bits 16-27 window (< 2^12) | bits 0-15 step (< 2^16)
+ *                 bits 52-53 kind (0 ENC, 1 INIT, 2 STEP, 3 MASK) | bits 28-51 unit (< 2^24) | bits 16-27 window (< 2^12) | bits 0-15 step (< 2^16)
  *               ENC : element index over the whole video's posterior noise [T,4,h,w] (window = step = 0);
  *               INIT: element index over the NEW frames [n,4,h,w] of window k (the overlap re-uses the previous window's initial noise);
- *               STEP: element index over the clip's [F,4,h,w] at window k, sampling step i.
+ *               STEP: element index over the clip's [F,4,h,w] at window k, sampling step i;
+ *               MASK: element index over the chunk's [F,4,h,w] of the mask estimate (section "a mask estimated from the prompt"):
+ *                     window = index of the chunk, step = index of the draw.
  *
  * insv2v_randn writes elements [offset, offset + n) of the stream (seed, stream) to out: fp32 normals, or with raw = 1 the 32-bit words'
  * bit patterns.  n and offset are 64-bit (offset + n may cross a multiple of 2^34, where the block index carries into its high word);
@@ -858,6 +860,45 @@ int insv2v_clip_scores(const void* img0, const void* img1, const void* txt0, con
  * of encode_image / encode_text (:25, :33; no eps, as there).  out may be x when x is fp32.  INSV2V_EINVAL: n or D <= 0, a row stride
  * below D, a NULL pointer. */
 int insv2v_l2_normalize(const void* x, int32_t fp32, int64_t ldx, float* out, int64_t ldo, int32_t n, int32_t D, insv2v_stream_t stream);
+
+/*
+ * ---- a mask estimated from the prompt (additions to ABI 15: no existing struct or entry changes) --------------------------------------
+ * Branches 1 and 2 of the 3-way CFG stack see the same latent and the same video condition and differ only in the text, so
+ * |eps3 - eps2| says where the instruction acts.  Averaged over n noised copies of the source latent, normalised by the video's mean,
+ * smoothed, thresholded and dilated it is the mask of a localized edit (DiffEdit's recipe; csrc/automask.hip, DESIGN.md section 18,
+ * tests/automask_ref.py restates the definition in float64).
+ */
+/* insv2v_build_unet_input for nbranch = 3 (same out / t_out layout, branch_rows, t_stride) whose latent channels are
+ * ka * latent + kb * noise: noise = the tensor `noise` [F,4,h,w] (seeded = 0), or element (flat index of [F,4,h,w]) i of the normal
+ * stream (seed, noise_stream) of the section "seeded noise" (seeded = 1, noise = NULL).  The fp16 values are bit-identical to
+ * insv2v_add_noise (after insv2v_randn for the seeded form) followed by insv2v_build_unet_input.  INSV2V_EINVAL: a NULL latent /
+ * img_cond / out, F, h or w <= 0, ldo < 8, both a tensor and seeded = 1 or neither, branch_rows below F*h*w (other than 0). */
+int insv2v_build_unet_input_noised(const float* latent, const float* img_cond, const float* noise, void* out, float* t_out,
+                                   float timestep, float ka, float kb, int64_t seed, int64_t noise_stream, int32_t seeded,
+                                   int32_t F, int32_t h, int32_t w, int32_t ldo, int64_t branch_rows, int32_t t_stride,
+                                   insv2v_stream_t stream);
+/* acc[F,h,w] (accumulate = 0: =, 1: +=) scale * sum over the 4 channels of |eps[2 bs + 4 pix + c] - eps[bs + 4 pix + c]|: eps is the
+ * UNet's channels-last fp32 output, bs = branch_stride fp32 elements between the branches (0 = 4*F*h*w) exactly as
+ * insv2v_step_desc.branch_stride; branch 0 and everything outside the two [F*h*w, 4] blocks is never read.  eps must be 16-byte
+ * aligned and bs a multiple of 4 (one 16-byte load per pixel and branch).  Order: s = (|d0| + |d1|) + (|d2| + |d3|), then
+ * acc = fma(scale, s, acc), or scale * s when accumulate = 0 (no memset is needed in front of the first draw). */
+int insv2v_eps_absdiff_accum(const float* eps, float* acc, int32_t F, int32_t h, int32_t w, int64_t branch_stride, float scale,
+                             int32_t accumulate, insv2v_stream_t stream);
+/* Bytes of workspace insv2v_automask_finish needs for a [T,h,w] map (the partial sums of its mean); INSV2V_EINVAL for a size <= 0. */
+int64_t insv2v_automask_workspace_bytes(int32_t T, int32_t h, int32_t w);
+/* raw fp32 [T,h,w] (>= 0) -> soft [T,h,w], mask_latent [T,h,w] (0 / 1) and mask [T,8h,8w] (every cell replicated 8 x 8, so
+ * insv2v_mask_to_latent returns mask_latent in both modes):
+ *   mean = mean(raw) over the whole map, a fixed-order fp32 reduction without atomics (two runs give the same bits);
+ *   soft0 = min(raw, clamp_ratio * mean) / (clamp_ratio * mean), 0 everywhere when mean == 0 (no division);
+ *   soft = soft0, or with smooth = 1 its temporal binomial [1,2,1]/4 over the T frames followed by the spatial 3 x 3 binomial
+ *          [1,2,1] x [1,2,1] / 16, edges replicated in both (T = 1: spatial only);
+ *   bin = soft > threshold (strict); mask_latent = max of bin over the (2 dilate + 1)^2 spatial square, zeros outside the frame.
+ * Nothing is allocated: the caller passes workspace (4-byte aligned) of at least insv2v_automask_workspace_bytes(T,h,w) bytes.
+ * INSV2V_EINVAL: a NULL pointer, T / h / w <= 0, threshold outside (0,1), clamp_ratio <= 0, dilate < 0, smooth outside {0,1}, a
+ * workspace that is too small, mask not 16-byte aligned, raw / soft / mask_latent overlapping one another. */
+int insv2v_automask_finish(const float* raw, float* soft, float* mask_latent, float* mask, void* workspace, int64_t workspace_bytes,
+                           int32_t T, int32_t h, int32_t w, float clamp_ratio, float threshold, int32_t smooth, int32_t dilate,
+                           insv2v_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -23,6 +23,13 @@ __device__ __forceinline__ float wave_max(float v) {
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
     return v;
 }
+// A latent re-noised to a level: ka z + kb n with BOTH products rounded before the sum (no contraction - what insv2v_add_noise has always
+// computed).  ONE copy: insv2v_add_noise and insv2v_build_unet_input_noised call it, so the latter's fp16 values are those of
+// add_noise followed by build_unet_input by construction.
+__device__ __forceinline__ float noised_f(float ka, float z, float kb, float n) {
+#pragma clang fp contract(off)
+    return ka * z + kb * n;
+}
 __device__ __forceinline__ float silu_f(float x) { return x / (1.0f + __expf(-x)); }
 __device__ __forceinline__ float quick_gelu_f(float x) { return x / (1.0f + __expf(-1.702f * x)); }  // x * sigmoid(1.702 x)
 // the optical-flow network's activations (INSV2V_ACT_RELU / SIGMOID / TANH; only the round-1 tile kernel's epilogue takes them)

@@ -281,7 +281,7 @@ extern "C" int insv2v_composite(const float* edited, const float* original, cons
 }
 __global__ __launch_bounds__(256) void add_noise_kernel(const float* z, const float* noise, float* out, int64_t n, float ka, float kb) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) out[i] = ka * z[i] + kb * noise[i];
+    if (i < n) out[i] = noised_f(ka, z[i], kb, noise[i]);
 }
 extern "C" int insv2v_add_noise(const float* z, const float* noise, float* out, int64_t n, float ka, float kb, insv2v_stream_t stream) {
     if (!z || !noise || !out || n < 0) return INSV2V_EINVAL;

@@ -203,6 +203,11 @@ SIGNATURES = {
     "insv2v_clip_preprocess": (c_i32, [C.POINTER(ClipPreprocessDesc), c_p]),
     "insv2v_clip_scores": (c_i32, [c_p, c_p, c_p, c_p, c_i32, c_i64, c_i64, c_i64, c_i32, c_i32, c_f32, c_p, c_p]),
     "insv2v_l2_normalize": (c_i32, [c_p, c_i32, c_i64, c_p, c_i64, c_i32, c_i32, c_p]),
+    "insv2v_build_unet_input_noised": (c_i32, [c_p, c_p, c_p, c_p, c_p, c_f32, c_f32, c_f32, c_i64, c_i64, c_i32,
+                                               c_i32, c_i32, c_i32, c_i32, c_i64, c_i32, c_p]),
+    "insv2v_eps_absdiff_accum": (c_i32, [c_p, c_p, c_i32, c_i32, c_i32, c_i64, c_f32, c_i32, c_p]),
+    "insv2v_automask_workspace_bytes": (c_i64, [c_i32, c_i32, c_i32]),
+    "insv2v_automask_finish": (c_i32, [c_p, c_p, c_p, c_p, c_p, c_i64, c_i32, c_i32, c_i32, c_f32, c_f32, c_i32, c_i32, c_p]),
 }
 
 _lib = None

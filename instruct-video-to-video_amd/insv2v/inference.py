@@ -20,8 +20,8 @@ import torch
 
 from . import ops
 from .fused import check_operand_windows
-from .rng import stream_id, STEP
-from .schedulers import DDIMScheduler, DDPMScheduler, DPMSolverMultistepScheduler
+from .rng import stream_id, STEP, MASK, WINDOW_BITS, STEP_BITS
+from .schedulers import DDIMScheduler, DDPMScheduler, DPMSolverMultistepScheduler, strength_to_start
 from .flow_utils import resize_flow
 
 
@@ -295,6 +295,51 @@ def check_known_region(latent, mask=None, source_latent=None, known_noise=None):
 
 
 _KNOWN_KEYS = ("mask", "source_latent", "known_noise")
+
+# ---- a mask estimated from the prompt -------------------------------------------------------------------------
+# Starting values, not findings: nobody has tuned them on a real checkpoint.
+AUTO_MASK_DEFAULTS = dict(n_maps=4, mask_strength=0.5, clamp_ratio=3.0, threshold=0.5, smooth=True, dilate=1)
+
+
+def check_automask_args(n_maps=4, mask_strength=0.5, clamp_ratio=3.0, threshold=0.5, smooth=True, dilate=1, frames_in_batch=16):
+    """Host-side check of ``estimate_mask``'s parameters (nothing is launched): ValueError naming the parameter."""
+    def integer(v, name):
+        if isinstance(v, bool) or not isinstance(v, int):
+            raise ValueError(f"estimate_mask: {name} must be an integer, got {v!r}")
+        return v
+    if not 1 <= integer(n_maps, "n_maps") < (1 << STEP_BITS):
+        raise ValueError(f"estimate_mask: n_maps = {n_maps} outside [1, 2^{STEP_BITS}) (the draw index of the MASK stream)")
+    try:
+        strength_to_start(mask_strength, 1)
+    except (TypeError, ValueError):
+        raise ValueError(f"estimate_mask: mask_strength must be in (0, 1], not {mask_strength!r}") from None
+    for name, v, ok in (("clamp_ratio", clamp_ratio, lambda x: x > 0.0 and x != float("inf")), ("threshold", threshold, lambda x: 0.0 < x < 1.0)):
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not ok(float(v)):   # (NaN fails every comparison)
+            raise ValueError(f"estimate_mask: {name} must be " + ("a positive number" if name == "clamp_ratio" else "inside (0, 1)") + f", not {v!r}")
+    if integer(dilate, "dilate") < 0:
+        raise ValueError(f"estimate_mask: dilate = {dilate} must not be negative")
+    if not isinstance(smooth, bool):
+        raise ValueError(f"estimate_mask: smooth must be True or False, not {smooth!r}")
+    if integer(frames_in_batch, "frames_in_batch") < 1:
+        raise ValueError(f"estimate_mask: frames_in_batch = {frames_in_batch} must be positive")
+
+
+def mask_plan(T, frames_in_batch, n_maps, cap):
+    """The UNet launches of one mask estimate, in order: ``(chunk, start, frames, draw0, clips)`` - chunk ``chunk`` = frames
+    [start, start + frames) of the video (consecutive chunks of ``frames_in_batch`` frames, no overlap, the last one whatever remains)
+    runs its draws [draw0, draw0 + clips) as the clips of one stacked launch; a chunk's ``n_maps`` draws are grouped by
+    ``stack_groups(n_maps, cap)``.  Pure arithmetic."""
+    T, fib, n_maps = int(T), int(frames_in_batch), int(n_maps)
+    if T < 1 or fib < 1 or n_maps < 1:
+        raise ValueError(f"mask_plan: {T} frames in chunks of {fib} with {n_maps} draws is not a plan")
+    groups = stack_groups(n_maps, cap)
+    plan = []
+    for k, start in enumerate(range(0, T, fib)):
+        d0 = 0
+        for m in groups:
+            plan.append((k, start, min(fib, T - start), d0, m))
+            d0 += m
+    return plan
 
 
 class InferenceIP2PVideo(Inference):
@@ -601,6 +646,72 @@ class InferenceIP2PVideo(Inference):
         for st, _ in gens:
             main.wait_stream(st)
         return results
+
+    # ---- a mask estimated from the prompt ---------------------------------------------------------------
+    @torch.no_grad()
+    def estimate_mask(self, source_latent, text_cond, text_uncond, img_cond, *, n_maps=4, mask_strength=0.5, clamp_ratio=3.0, threshold=0.5,
+                      smooth=True, dilate=1, frames_in_batch=16, noises=None, seed=None, unit=0):
+        """Where does the instruction act?  -> dict(raw, soft, mask_latent [1,T,h,w], mask [1,T,8h,8w]) for a whole video's SCALED
+        source latent ``source_latent`` [1,T,4,h,w] and its condition ``img_cond`` = source_latent / scale_factor (DESIGN.md section 18;
+        tests/automask_ref.py is the definition).  Branches 1 and 2 of the CFG stack differ only in the text, so
+        ``raw = 1/(4 n_maps) sum_draws sum_c |eps3 - eps2|`` at the source latent noised to the level of ``mask_strength``
+        (``timesteps[strength_to_start(mask_strength, steps)[1]]``) is the instruction's footprint; it is normalised by
+        ``clamp_ratio`` x the VIDEO's mean, smoothed (``smooth``), thresholded (strict ``>``) and dilated by ``dilate`` cells.
+        ``mask`` feeds ``edit_video(mask=...)`` / ``__call__(mask=...)`` unchanged; ``ops.mask_to_latent`` of it is ``mask_latent`` in both modes.
+
+        The video is cut into consecutive chunks of ``frames_in_batch`` frames (no overlap); a chunk's draws are the clips of the
+        branch-major stacked runner (``mask_plan``).  The estimate runs in launches of its own - never stacked with another unit or with
+        sampling - so with a ``seed`` the mask is a pure function of (seed, unit, inputs, parameters).  Noise, in order of precedence:
+        ``noises[chunk][draw]`` ([1,F,4,h,w] or [F,4,h,w] tensors), the seeded stream ``stream_id(MASK, unit, chunk, draw)`` generated
+        inside the input kernel, ``torch.randn``.  The defaults are starting values, not findings."""
+        check_automask_args(n_maps, mask_strength, clamp_ratio, threshold, smooth, dilate, frames_in_batch)
+        if not torch.is_tensor(source_latent) or source_latent.dim() != 5 or source_latent.shape[0] != 1:
+            raise ValueError(f"estimate_mask: source_latent {tuple(getattr(source_latent, 'shape', ()))} must be [1,T,4,h,w] (one unit per estimate)")
+        z, cond = self._clip_tensors(source_latent, img_cond)
+        T, _, h, w = z.shape
+        nchunks = -(-T // frames_in_batch)
+        if nchunks > (1 << WINDOW_BITS):
+            raise ValueError(f"estimate_mask: {T} frames in chunks of {frames_in_batch} are {nchunks} chunks, more than the 2^{WINDOW_BITS} a stream id numbers")
+        if noises is not None:
+            if len(noises) != nchunks or any(len(nc) != n_maps for nc in noises):
+                raise ValueError(f"estimate_mask: noises must hold {nchunks} chunks of {n_maps} draws each")
+            for k, nc in enumerate(noises):
+                want = (min(frames_in_batch, T - k * frames_in_batch), 4, h, w)
+                if any(not torch.is_tensor(x) or tuple(x.shape[-4:]) != want or x.numel() != want[0] * 4 * h * w for x in nc):
+                    raise ValueError(f"estimate_mask: every draw of chunk {k} must be shaped {want}")
+        elif seed is not None:
+            stream_id(MASK, unit, nchunks - 1, n_maps - 1)   # the ranges, before anything is launched
+        L = text_cond.shape[1]
+        plan = mask_plan(T, frames_in_batch, n_maps, max_clips_in_flight(min(T, frames_in_batch), h, w))
+        for F, m in sorted({(p[2], p[4]) for p in plan}):   # every launch's geometry is checked before the first one
+            check_operand_windows(3 * m, F, h, w, _unet_channels(self.unet), L)
+        dev = z.device
+        t = int(self.scheduler.timesteps[strength_to_start(mask_strength, self.num_ddim_steps)[1]])
+        ka, kb = self.scheduler.start_coefficients(t)
+        raw = torch.empty((T, h, w), device=dev, dtype=torch.float32)   # (the first draw of every chunk writes, the others add: no memset)
+        scale = 1.0 / (4.0 * n_maps)
+        ready = set()
+        for k, start, F, d0, m in plan:
+            runner = shared_runner(self.unet, 3 * m, F, h, w, L, 0, self.use_graph, False, cfg_clips=m)
+            if id(runner) not in ready:   # the context of a stack of m draws depends on m alone
+                runner.set_context(torch.cat([text_uncond] * (2 * m) + [text_cond] * m, dim=0))
+                ready.add(id(runner))
+            rows1 = F * h * w
+            zc, cc = z[start:start + F], cond[start:start + F]
+            for c in range(m):
+                src = {}
+                if noises is not None:
+                    src["noise"] = noises[k][d0 + c].to(device=dev, dtype=torch.float32).reshape(F, 4, h, w).contiguous()
+                elif seed is not None:
+                    src.update(seed=seed, stream=stream_id(MASK, unit, k, d0 + c))
+                else:
+                    src["noise"] = torch.randn((F, 4, h, w), device=dev, dtype=torch.float32)
+                ops.build_unet_input_noised(zc, cc, runner.x_in[c * rows1:], runner.t[c:], t, ka, kb, branch_rows=m * rows1, t_stride=m, **src)
+            eps = runner.run()
+            for c in range(m):
+                ops.eps_absdiff_accum(eps[c * rows1:], raw[start:start + F], scale, accumulate=d0 + c > 0, branch_stride=m * rows1 * 4)
+        soft, mask_latent, mask = ops.automask_finish(raw, clamp_ratio=float(clamp_ratio), threshold=float(threshold), smooth=smooth, dilate=dilate)
+        return {"raw": raw[None], "soft": soft[None], "mask_latent": mask_latent[None], "mask": mask[None]}
 
     # ---- reference call surface ----------------------------------------------------------------------
     @torch.no_grad()

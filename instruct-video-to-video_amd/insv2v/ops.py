@@ -838,6 +838,71 @@ def add_noise(z, noise, ka, kb):
     return out
 
 
+def build_unet_input_noised(latent, img_cond, out, t_out, timestep, ka, kb, *, noise=None, seed=None, stream=0, branch_rows=0, t_stride=0):
+    """``build_unet_input`` for the three CFG branches whose latent is ``ka * latent + kb * noise`` (insv2v_build_unet_input_noised):
+    ``noise`` fp32 [F,4,h,w], or - ``seed`` / ``stream`` - generated inside the kernel from the seeded stream (element = flat index of
+    [F,4,h,w]); passing both, or neither, is refused.  Bit-identical to ``add_noise`` (+ ``randn``) followed by ``build_unet_input``."""
+    lib = _lib.load()
+    _req(latent, torch.float32, "build_unet_input_noised.latent"), _req(img_cond, torch.float32, "build_unet_input_noised.img_cond")
+    if (noise is None) == (seed is None):
+        raise _lib.HipKernelError("build_unet_input_noised: pass noise or seed, exactly one of them")
+    shape = tuple(latent.shape[-4:])
+    for name, t in (("latent", latent), ("img_cond", img_cond), ("noise", noise)):
+        if t is not None and (tuple(t.shape[-4:]) != shape or t.numel() != math.prod(shape) or not t.is_contiguous()):
+            raise _lib.HipKernelError(f"build_unet_input_noised: {name} {tuple(t.shape)} must be contiguous and shaped {shape}")
+    if noise is not None:
+        _req(noise, torch.float32, "build_unet_input_noised.noise")
+    F, _, h, w = shape
+    rows = F * h * w
+    _req(out, torch.float16, "build_unet_input_noised.out")
+    if out.dim() != 2 or not out.is_contiguous() or out.shape[0] < 2 * (branch_rows or rows) + rows:   # the three branches must lie inside out
+        raise _lib.HipKernelError(f"build_unet_input_noised: out {tuple(out.shape)} does not hold 3 branches of {rows} rows at stride {branch_rows or rows}")
+    if t_out is not None and (_req(t_out, torch.float32, "build_unet_input_noised.t_out").numel() < 2 * (t_stride or 1) + 1 or not t_out.is_contiguous()):
+        raise _lib.HipKernelError(f"build_unet_input_noised: t_out {tuple(t_out.shape)} does not hold 3 entries at stride {t_stride or 1}")
+    check(lib.insv2v_build_unet_input_noised(latent.data_ptr(), img_cond.data_ptr(), _ptr(noise), out.data_ptr(), _ptr(t_out), float(timestep),
+                                             ka, kb, as_int64(seed) if seed is not None else 0, as_int64(stream, "stream"),
+                                             int(seed is not None), F, h, w, out.shape[-1], branch_rows, t_stride, _stream()),
+          "insv2v_build_unet_input_noised")
+    return out
+
+
+def eps_absdiff_accum(eps, acc, scale, *, accumulate, branch_stride=0):
+    """acc [F,h,w] (``accumulate``: +=, else =) ``scale`` * sum_c |eps3 - eps2| from the UNet's channels-last fp32 output ``eps`` (a view
+    that starts at the clip's first branch; ``branch_stride`` fp32 elements between the branches as for ``cfg_step``, 0 = back to back).
+    Branch 0 is not read."""
+    lib = _lib.load()
+    _req(eps, torch.float32, "eps_absdiff_accum.eps"), _req(acc, torch.float32, "eps_absdiff_accum.acc")
+    if acc.dim() < 3 or not acc.is_contiguous() or acc.numel() != math.prod(acc.shape[-3:]):
+        raise _lib.HipKernelError(f"eps_absdiff_accum: acc {tuple(acc.shape)} must be a contiguous [F,h,w]")
+    F, h, w = acc.shape[-3:]
+    bs = branch_stride if branch_stride > 0 else 4 * F * h * w
+    if not eps.is_contiguous() or eps.numel() < 2 * bs + 4 * F * h * w:
+        raise _lib.HipKernelError(f"eps_absdiff_accum: eps ({eps.numel()} elements) does not hold branches 1 and 2 of [{F},{h},{w},4] at stride {bs}")
+    check(lib.insv2v_eps_absdiff_accum(eps.data_ptr(), acc.data_ptr(), F, h, w, branch_stride, scale, int(bool(accumulate)), _stream()),
+          "insv2v_eps_absdiff_accum")
+    return acc
+
+
+def automask_finish(raw, *, clamp_ratio=3.0, threshold=0.5, smooth=True, dilate=1):
+    """raw fp32 [T,h,w] -> (soft [T,h,w], mask_latent [T,h,w] of 0 / 1, mask [T,8h,8w]): insv2v_automask_finish - the video's mean (a
+    fixed-order reduction), ``min(raw, r mean) / (r mean)``, the optional temporal + spatial binomial smoothing, ``> threshold``, the
+    spatial dilation and the 8 x 8 replication (tests/automask_ref.py is the definition)."""
+    lib = _lib.load()
+    _req(raw, torch.float32, "automask_finish.raw")
+    if raw.dim() != 3 or not raw.is_contiguous():
+        raise _lib.HipKernelError(f"automask_finish: raw {tuple(raw.shape)} must be a contiguous [T,h,w]")
+    T, h, w = raw.shape
+    soft, mask_latent = torch.empty_like(raw), torch.empty_like(raw)
+    mask = torch.empty((T, 8 * h, 8 * w), device=raw.device, dtype=torch.float32)
+    nbytes = lib.insv2v_automask_workspace_bytes(T, h, w)
+    if nbytes <= 0:
+        raise _lib.HipKernelError(f"automask_finish: no workspace size for raw {tuple(raw.shape)}")
+    ws = torch.empty((nbytes + 3) // 4, device=raw.device, dtype=torch.float32)
+    check(lib.insv2v_automask_finish(raw.data_ptr(), soft.data_ptr(), mask_latent.data_ptr(), mask.data_ptr(), ws.data_ptr(), ws.numel() * 4,
+                                     T, h, w, clamp_ratio, threshold, int(bool(smooth)), int(dilate), _stream()), "insv2v_automask_finish")
+    return soft, mask_latent, mask
+
+
 def _fill_step_desc(d, eps_in, latent, *, nbranch, text_cfg=1.0, img_cfg=1.0, sqrt_a=1.0, sqrt_1ma=0.0, coef=(0, 0, 0, 0),
                     latent_out=None, pred_x0=None, eps_out=None, latent_ref=None, correct=0, delta_q=None, noise=None,
                     rescale_stats=None, guidance_rescale=0.0, branch_stride=0, noise_seed=None, noise_stream=0):

@@ -48,12 +48,34 @@ def _seeded(seed, unit):
 MASK_MODES = ("mean", "max")
 
 
-def check_edit_args(frames_shape, mask=None, strength=1.0, mask_mode="max"):
+AUTO_MASK_KEYS = ("n_maps", "mask_strength", "clamp_ratio", "threshold", "smooth", "dilate", "frames_in_batch", "noises")
+
+
+def check_edit_args(frames_shape, mask=None, strength=1.0, mask_mode="max", auto_mask=None):
     """Host-side check of the localized / partial edit controls (nothing is launched): ``strength`` in (0, 1], ``mask_mode`` "mean" or
-    "max", ``mask`` a floating-point [1,T,H,W] or [1,1,H,W] tensor for frames [1,T,3,H,W] with H and W multiples of 8."""
+    "max", ``mask`` a floating-point [1,T,H,W] or [1,1,H,W] tensor for frames [1,T,3,H,W] with H and W multiples of 8 - or the string
+    "auto" (the mask is estimated from the prompt, ``InferenceIP2PVideo.estimate_mask``), then optionally with ``auto_mask``, a dict of
+    that method's keywords (``AUTO_MASK_KEYS``)."""
     strength_to_start(strength, 1)
     if mask_mode not in MASK_MODES:
         raise ValueError(f"mask_mode {mask_mode!r} is neither 'mean' nor 'max'")
+    if auto_mask is not None and not (isinstance(mask, str) and mask == "auto"):
+        raise ValueError("auto_mask holds the parameters of an estimated mask: pass mask=\"auto\" with it")
+    if isinstance(mask, str):
+        if mask != "auto":
+            raise ValueError(f"mask must be a tensor, None or the string \"auto\", not {mask!r}")
+        b, _, _, H, W = frames_shape
+        if b != 1 or H % 8 or W % 8:
+            raise ValueError(f"mask=\"auto\" needs frames [1,T,3,H,W] with H and W multiples of 8 (one latent cell per 8x8 pixels), not {tuple(frames_shape)}")
+        if auto_mask is not None:
+            from .inference import check_automask_args
+            if not isinstance(auto_mask, dict) or set(auto_mask) - set(AUTO_MASK_KEYS):
+                raise ValueError(f"auto_mask (the parameters of mask=\"auto\") must be a dict with keys among {AUTO_MASK_KEYS}, got {auto_mask!r}")
+            try:
+                check_automask_args(**{k: v for k, v in auto_mask.items() if k != "noises"})
+            except ValueError as e:
+                raise ValueError(f"auto_mask (the parameters of mask=\"auto\"): {e}") from None
+        return
     if mask is None:
         return
     b, T, _, H, W = frames_shape
@@ -117,10 +139,25 @@ class _EditPlan:
         return ops.composite(img, orig, self.mask_img, out=img)[None]
 
 
+def _estimate_mask(model, inf_pipe, z, cond, text_cond, text_uncond, frames_in_batch, auto_mask, seed, unit):
+    """``mask="auto"``: the unit's mask, estimated ONCE from the whole video in launches of its own, before its first window
+    (``InferenceIP2PVideo.estimate_mask``) -> its result dict; ``["mask"]`` [1,T,H,W] then goes through ``_EditPlan`` like a user's."""
+    if z is None:   # (a caller's ``cond`` is z / scale_factor)
+        z = cond * model.scale_factor
+    kw = dict(frames_in_batch=frames_in_batch)
+    kw.update(auto_mask or {})
+    return inf_pipe.estimate_mask(z, text_cond, text_uncond, cond, **kw, **_seeded(seed, unit))
+
+
+def _result(image, latent, est, return_latent, return_mask):
+    out = (image,) + ((latent,) if return_latent else ()) + ((est,) if return_mask else ())
+    return out if len(out) > 1 else image
+
+
 @torch.no_grad()
 def edit_video(model, inf_pipe, frames, text_cond, text_uncond, text_cfg=7.5, video_cfg=1.8, frames_in_batch=16,
                num_ref_frames=4, init_noises=None, enc_noise=None, flows_per_window=None, return_latent=False, cond=None,
-               seed=None, unit=0, mask=None, strength=1.0, mask_mode="max"):
+               seed=None, unit=0, mask=None, strength=1.0, mask_mode="max", auto_mask=None, return_mask=False):
     """frames [1,T,3,H,W] in [-1,1] -> edited frames [1,T,3,H,W] clipped to [-1,1].
 
     ``seed`` (default None: every draw comes from the global torch generators, as before) makes the edit reproducible: the posterior
@@ -141,13 +178,24 @@ def edit_video(model, inf_pipe, frames, text_cond, text_uncond, text_cfg=7.5, vi
     every step holds the latent outside it at the source video's, re-noised to that step's level with the window's initial noise
     (inside the step kernel), and the result is composited against the input frames, so pixels outside the mask ARE the input's.
     ``strength`` in (0, 1] makes the edit partial: only the last ``round(strength * steps)`` steps run, and at every strength below
-    1.0 - also one that rounds to all steps - from the source latent noised to the first executed step's level instead of from pure noise.  With ``mask=None, strength=1.0`` the calls are exactly what they were."""
-    check_edit_args(frames.shape, mask, strength, mask_mode)
+    1.0 - also one that rounds to all steps - from the source latent noised to the first executed step's level instead of from pure noise.  With ``mask=None, strength=1.0`` the calls are exactly what they were.
+
+    ``mask="auto"``: nobody drew a mask - it is estimated from the prompt, once per unit from the whole video and before the first
+    window (``InferenceIP2PVideo.estimate_mask``), and then used exactly as a user's mask would be (it is constant
+    over every 8x8 cell, so ``mask_mode`` has no effect on it).  ``auto_mask``: a dict of the estimator's keywords (``AUTO_MASK_KEYS``;
+    default: its defaults, chunks of ``frames_in_batch`` frames); with ``seed`` the estimate's noise comes from the unit's MASK streams.
+    ``return_mask=True`` appends the estimator's result dict (``raw``, ``soft``, ``mask_latent``, ``mask``; None without ``mask="auto"``)
+    to the returned tuple."""
+    check_edit_args(frames.shape, mask, strength, mask_mode, auto_mask)
     dev = model.unet.device
     z = None
     if cond is None:
         z = model.encode_image_to_latent(frames, enc_noise, **_seeded(seed, unit))
         cond = z / model.scale_factor
+    est = None
+    if isinstance(mask, str):   # "auto" (check_edit_args)
+        est = _estimate_mask(model, inf_pipe, z, cond, text_cond, text_uncond, frames_in_batch, auto_mask, seed, unit)
+        mask = est["mask"]
     conds, refs = split_batch(cond, frames_in_batch, num_ref_frames)
     plan = _EditPlan(model, inf_pipe, frames, cond, mask, strength, mask_mode, frames_in_batch, num_ref_frames, z=z)
     frame_chunks, _ = split_batch(frames, frames_in_batch, num_ref_frames)
@@ -185,11 +233,11 @@ def edit_video(model, inf_pipe, frames, text_cond, text_uncond, text_cfg=7.5, vi
         preds.append(pred[:, R:])
     latent = torch.cat(preds, dim=1)
     image = plan.finish(model.decode_latent_to_image(latent), frames)
-    return (image, latent) if return_latent else image
+    return _result(image, latent, est, return_latent, return_mask)
 
 
 @torch.no_grad()
-def edit_videos(model, inf_pipe, units, frames_in_batch=16, num_ref_frames=4, return_latent=False, seed=None, max_clips=None):
+def edit_videos(model, inf_pipe, units, frames_in_batch=16, num_ref_frames=4, return_latent=False, seed=None, max_clips=None, return_mask=False):
     """Several independent units at once - the throughput form of ``edit_video`` (the reference's unit loop offers them naturally: four
     prompts per video, insv2v_run_loveu_tgve.py:83,101): window k of ALL units runs as one stacked launch chain
     (``InferenceIP2PVideo.run_stacked``: B = 3 x units in every UNet launch, weights read once, every launch fills the chip), windows
@@ -204,19 +252,22 @@ def edit_videos(model, inf_pipe, units, frames_in_batch=16, num_ref_frames=4, re
     ``max_clips``: units per launch chain, as for ``run_stacked`` (None: its default cap, ``max_clips_in_flight``).
     A unit may carry ``mask``, ``strength`` and ``mask_mode`` as for ``edit_video``: masked and unmasked units stack together; the units
     of one call must share the number of executed steps (a stack shares ``start_time``), so strengths that round to different step
-    counts raise ValueError."""
+    counts raise ValueError.  A unit may also carry ``mask="auto"`` (and ``auto_mask``): its mask is estimated alone, in launches of its
+    own, before the stacked windows start - so it is bit for bit the mask ``edit_video`` estimates for that unit.  ``return_mask``: as
+    for ``edit_video``, per unit."""
     if len(units) == 0:
         return []
     for u in units:
-        check_edit_args(u["frames"].shape, u.get("mask"), u.get("strength", 1.0), u.get("mask_mode", "max"))
+        check_edit_args(u["frames"].shape, u.get("mask"), u.get("strength", 1.0), u.get("mask_mode", "max"), u.get("auto_mask"))
     if len({_start_time(inf_pipe, u.get("strength", 1.0)) for u in units}) > 1:
         raise ValueError("edit_videos: the units of one call must share the number of executed steps (strength); edit the others separately")
     wants_flow = hasattr(inf_pipe, "obtain_flow_batched")
     ids = [u.get("unit", j) for j, u in enumerate(units)]
     if len(units) == 1:
-        keys = ("text_cfg", "video_cfg", "init_noises", "enc_noise", "cond", "flows_per_window", "mask", "strength", "mask_mode")
+        keys = ("text_cfg", "video_cfg", "init_noises", "enc_noise", "cond", "flows_per_window", "mask", "strength", "mask_mode", "auto_mask")
+        more = {"return_mask": True} if return_mask else {}   # (a plain call carries no new keyword)
         return [edit_video(model, inf_pipe, u["frames"], u["text_cond"], u["text_uncond"], frames_in_batch=frames_in_batch,
-                           num_ref_frames=num_ref_frames, return_latent=return_latent, seed=seed, unit=ids[0],
+                           num_ref_frames=num_ref_frames, return_latent=return_latent, seed=seed, unit=ids[0], **more,
                            **{k: u[k] for k in keys if k in u}) for u in units]
     dev = model.unet.device
     cap = {} if max_clips is None else {"max_clips": max_clips}   # (a pipe without the parameter keeps working with the default)
@@ -230,11 +281,15 @@ def edit_videos(model, inf_pipe, units, frames_in_batch=16, num_ref_frames=4, re
             z = model.encode_image_to_latent(u["frames"], u.get("enc_noise"), **_seeded(seed, uid))
             cond = z / model.scale_factor
         conds, refs = split_batch(cond, frames_in_batch, num_ref_frames)
-        plan = _EditPlan(model, inf_pipe, u["frames"], cond, u.get("mask"), u.get("strength", 1.0), u.get("mask_mode", "max"),
+        mask, est = u.get("mask"), None
+        if isinstance(mask, str):   # "auto": estimated here, alone, before the first stacked window of any unit
+            est = _estimate_mask(model, inf_pipe, z, cond, u["text_cond"], u["text_uncond"], frames_in_batch, u.get("auto_mask"), seed, uid)
+            mask = est["mask"]
+        plan = _EditPlan(model, inf_pipe, u["frames"], cond, mask, u.get("strength", 1.0), u.get("mask_mode", "max"),
                          frames_in_batch, num_ref_frames, z=z)
         if wants_flow and u.get("flows_per_window") is None and getattr(inf_pipe, "flow_estimator", None) is None and len(conds) > 1:
             raise RuntimeError("optical-flow pipeline without a flow source: pass flows_per_window= or build the pipe with flow_estimator=")
-        st.append(dict(u=u, unit=uid, conds=conds, refs=refs, preds=[], init=None, pred=None, plan=plan,
+        st.append(dict(u=u, unit=uid, conds=conds, refs=refs, preds=[], init=None, pred=None, plan=plan, est=est,
                        frame_chunks=split_batch(u["frames"], frames_in_batch, num_ref_frames)[0] if wants_flow else None))
 
     def draw(s, k, like):
@@ -280,7 +335,7 @@ def edit_videos(model, inf_pipe, units, frames_in_batch=16, num_ref_frames=4, re
     for s in st:
         latent = torch.cat(s["preds"], dim=1)
         image = s["plan"].finish(model.decode_latent_to_image(latent), s["u"]["frames"])
-        outs.append((image, latent) if return_latent else image)
+        outs.append(_result(image, latent, s["est"], return_latent, return_mask))
     return outs
 
 
@@ -319,6 +374,14 @@ def build_parser():
                    help="mean | max: how an image-resolution mask (the optional \"mask\" entry of a --units file, [n,T,H,W] or [n,1,H,W]; "
                         "--synthetic-mask) is reduced to one value per 8x8 latent cell")
     p.add_argument("--synthetic-mask", action="store_true", help="with --synthetic: edit only a centred rectangle (half the height and width) of every frame")
+    p.add_argument("--auto-mask", action="store_true",
+                   help="localized edit without a drawn mask: every unit's mask is estimated from its prompt (InferenceIP2PVideo.estimate_mask) "
+                        "before its first window; the --auto-mask-* values are starting points, not tuned on a real checkpoint")
+    p.add_argument("--auto-mask-maps", type=int, default=4, help="noised copies of the source latent the estimate averages over")
+    p.add_argument("--auto-mask-strength", type=float, default=0.5, help="in (0, 1]: the noise level of those copies, as --strength")
+    p.add_argument("--auto-mask-threshold", type=float, default=0.5, help="in (0, 1): a cell is edited where the normalised map exceeds it")
+    p.add_argument("--auto-mask-dilate", type=int, default=1, help="latent cells the thresholded mask is grown by")
+    p.add_argument("--mask-out", type=str, default=None, help=".pt file for the estimated masks: {unit id: {mask_latent, soft}} (with --auto-mask)")
     p.add_argument("--raft-ckpt", type=str, default=None,
                    help="torchvision raft_large checkpoint (state dict) for --with_optical_flow: the estimator runs on the HIP kernels")
     p.add_argument("--flows", type=str, default=None,
@@ -349,6 +412,16 @@ def check_args(args):
         raise SystemExit(f"--mask-mode must be mean or max, not {args.mask_mode}")
     if getattr(args, "synthetic_mask", False) and not args.synthetic:
         raise SystemExit("--synthetic-mask needs --synthetic N (masks of real units come from the \"mask\" entry of a --units file)")
+    if hasattr(args, "auto_mask_maps"):   # (out-of-range values are refused with or without --auto-mask)
+        from .inference import check_automask_args
+        try:
+            check_automask_args(**auto_mask_kwargs(args))
+        except ValueError as e:
+            raise SystemExit(f"--auto-mask-maps / --auto-mask-strength / --auto-mask-threshold / --auto-mask-dilate: {e}")
+    if getattr(args, "auto_mask", False) and getattr(args, "synthetic_mask", False):
+        raise SystemExit("--auto-mask and --synthetic-mask are two masks: pass one")
+    if getattr(args, "mask_out", None) and not getattr(args, "auto_mask", False):
+        raise SystemExit("--mask-out holds the estimated masks: it needs --auto-mask")
     if args.flows and args.units is None and not args.synthetic:
         raise SystemExit("--flows is supported with --units / --synthetic (flows are indexed by unit)")
     score_synth, score_ckpt, score_out = (getattr(args, k, None) for k in ("score_synthetic", "score_ckpt", "score_out"))
@@ -392,6 +465,29 @@ def write_scores(path, records, rank=0, world=1):
         json.dump(sorted(records, key=lambda r: r["unit"]), f, indent=1)
 
 
+def auto_mask_kwargs(args):
+    """The estimator's keywords of the --auto-mask-* flags."""
+    return dict(n_maps=args.auto_mask_maps, mask_strength=args.auto_mask_strength, threshold=args.auto_mask_threshold, dilate=args.auto_mask_dilate)
+
+
+def auto_mask_unit(args, data=None):
+    """What --auto-mask adds to every unit (nothing without it).  A --units file that carries its own ``mask`` entry is refused."""
+    if not getattr(args, "auto_mask", False):
+        return {}
+    if data is not None and data.get("mask") is not None:
+        raise SystemExit("--auto-mask estimates every unit's mask, but the --units file holds a \"mask\" entry: pass one of the two")
+    return dict(mask="auto", auto_mask=auto_mask_kwargs(args))
+
+
+def write_masks(path, records, rank=0, world=1):
+    """{unit id: {"mask_latent": [T,h,w], "soft": [T,h,w]}} of this rank's units (with several ranks each writes its own FILE.rankR.pt)."""
+    if world > 1:
+        root, ext = os.path.splitext(path)
+        path = f"{root}.rank{rank}{ext}"
+    os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
+    torch.save({int(u): {k: est[k][0].cpu() for k in ("mask_latent", "soft")} for u, est in sorted(records.items())}, path)
+
+
 def synthetic_mask(n, H, W):
     """[n,1,H,W]: 1 inside the centred rectangle of half the height and width, 0 outside (--synthetic-mask)."""
     m = torch.zeros((n, 1, H, W), dtype=torch.float32)
@@ -425,6 +521,9 @@ def run_dataset(args, model, pipe, rank=0, world=1, scorer=None):
     seed = getattr(args, "seed", None)
     kinds = ("style", "object", "background", "multiple")
     records = []
+    auto = auto_mask_unit(args)
+    want_masks = {"return_mask": True} if auto and getattr(args, "mask_out", None) else {}   # (a plain run carries no new keyword)
+    masks = {}
     for ci, (video_id, text_cfg, video_cfg, num_frames, image_size) in enumerate(combos):
         if ci % world != rank:
             continue
@@ -444,19 +543,23 @@ def run_dataset(args, model, pipe, rank=0, world=1, scorer=None):
                 continue
             todo.append((gif_path, image_dir, dict(frames=frames, text_cond=model.encode_text([prompt]), text_uncond=text_uncond,
                                                    text_cfg=text_cfg, video_cfg=video_cfg, cond=cond, unit=4 * ci + kinds.index(key),
-                                                   strength=getattr(args, "strength", 1.0)), prompt))
+                                                   strength=getattr(args, "strength", 1.0), **auto), prompt))
         # the four prompts of a video share the conditioning latent and the window plan: one stacked launch chain per window (B = 12)
         if getattr(args, "no_stack", False):
-            edits = [edit_videos(model, pipe, [u], seed=seed)[0] for _, _, u, _ in todo]
+            edits = [edit_videos(model, pipe, [u], seed=seed, **want_masks)[0] for _, _, u, _ in todo]
         else:
-            edits = edit_videos(model, pipe, [u for _, _, u, _ in todo], seed=seed, max_clips=getattr(args, "max_stack", None))
+            edits = edit_videos(model, pipe, [u for _, _, u, _ in todo], seed=seed, max_clips=getattr(args, "max_stack", None), **want_masks)
         for (gif_path, image_dir, u, prompt), edited in zip(todo, edits):
+            if want_masks:
+                edited, masks[u["unit"]] = edited
             if scorer is not None:   # the edited frames are still on the device
                 records.append(score_record(scorer, u["unit"], frames, edited, batch["original"], prompt))
             save_tensor_to_gif(torch.cat([frames.float().cpu(), edited.float().cpu()], dim=4), gif_path, fps=5)
             save_tensor_to_images(edited.float().cpu(), image_dir)
     if scorer is not None:
         write_scores(args.score_out, records, rank, world)
+    if want_masks:
+        write_masks(args.mask_out, masks, rank, world)
 
 
 def _score_texts(data, i, scorer):
@@ -523,8 +626,11 @@ def main(argv=None):
     n = data["frames"].shape[0]
     flows = torch.load(args.flows, map_location="cpu") if args.flows else None
     item_shape = tuple(data["frames"].shape[1:])  # a rank without units still takes part in the all_gather
+    auto = auto_mask_unit(args, data)   # (refuses --auto-mask next to a "mask" entry of the file)
+    want_masks = {"return_mask": True} if auto and args.mask_out else {}
+    est_masks = {}
     masks = data.get("mask")   # optional [n,T,H,W] / [n,1,H,W]
-    edit = lambda i: dict(mask=masks[i:i + 1] if masks is not None else None, strength=args.strength, mask_mode=args.mask_mode)
+    edit = lambda i: dict(dict(mask=masks[i:i + 1] if masks is not None else None, strength=args.strength, mask_mode=args.mask_mode), **auto)
     scorer = build_scorer(args, f"cuda:{local}", tok)
     records = []
     outs = []
@@ -535,7 +641,7 @@ def main(argv=None):
         if args.no_stack:
             local_out = [edit_video(model, pipe, data["frames"][i:i + 1], data["text_cond"][i:i + 1], data["text_uncond"],
                                     text_cfg, video_cfg, flows_per_window=flows[i] if flows is not None else None,
-                                    seed=args.seed, unit=ci * n + i, **edit(i)) for i in mine]
+                                    seed=args.seed, unit=ci * n + i, **edit(i), **want_masks) for i in mine]
         else:   # a rank's units as stacked launch chains (run_stacked caps the stack at what the kernels' operand window allows)
             from .inference import max_clips_in_flight
             T, S = data["frames"].shape[1], data["frames"].shape[-1]
@@ -545,13 +651,19 @@ def main(argv=None):
                 local_out += edit_videos(model, pipe, [dict(frames=data["frames"][i:i + 1], text_cond=data["text_cond"][i:i + 1],
                                                             text_uncond=data["text_uncond"], text_cfg=text_cfg, video_cfg=video_cfg, unit=ci * n + i, **edit(i),
                                                             **({"flows_per_window": flows[i]} if flows is not None else {}))
-                                                       for i in mine[g:g + cap]], seed=args.seed, max_clips=args.max_stack)
+                                                       for i in mine[g:g + cap]], seed=args.seed, max_clips=args.max_stack, **want_masks)
+        if want_masks:
+            for i, (_, est) in zip(mine, local_out):
+                est_masks[ci * n + i] = est
+            local_out = [img for img, _ in local_out]
         for i, edited in zip(mine, local_out if scorer is not None else []):
             records.append(score_record(scorer, ci * n + i, data["frames"][i:i + 1], edited, *_score_texts(data, i, scorer)))
         local_out = torch.cat(local_out, 0).half() if local_out else torch.zeros((0, *item_shape), device=model.unet.device).half()
         outs.append(gather_frames(local_out, n, item_shape=item_shape))
     if scorer is not None:
         write_scores(args.score_out, records, rank, world)
+    if want_masks:
+        write_masks(args.mask_out, est_masks, rank, world)
     if rank == 0:
         os.makedirs(os.path.dirname(args.out) or ".", exist_ok=True)
         torch.save(torch.stack(outs, 0).cpu(), args.out)
