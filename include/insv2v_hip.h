@@ -900,6 +900,38 @@ int insv2v_automask_finish(const float* raw, float* soft, float* mask_latent, fl
                            int32_t T, int32_t h, int32_t w, float clamp_ratio, float threshold, int32_t smooth, int32_t dilate,
                            insv2v_stream_t stream);
 
+/*
+ * ---- a key-frame mask tracked with optical flow (an addition to ABI 15: no existing struct or entry changes) --------------------------
+ * One step of the chain that carries a mask drawn on ONE frame k to every frame (csrc/masktrack.hip, DESIGN.md section 19;
+ * tests/masktrack_ref.py restates the definition in float64).  The mask is never warped frame by frame: every frame t keeps F_t, the
+ * displacement of its pixels to their position in the key frame, and samples the key mask M once.  From the chain's previous frame t'
+ * (F_k = 0, V_k = 1) with b = the flow defined on t that points into t' (the convention of insv2v_warp_image: sampling t' at x + b(x)
+ * gives t) and, optionally, c = the opposite flow defined on t', per pixel (x, y):
+ *   p    = (x + b_x, y + b_y);  inb = 0 <= p_x <= W-1 and 0 <= p_y <= H-1;  pc = p clamped to the frame
+ *   S(G) = bilinear sample of G at pc: x0 = floor(pc_x), x1 = min(x0 + 1, W-1), the same in y (border clamp, NOT zero padding), as
+ *          lerps: top + ay (bottom - top), top = g00 + ax (g01 - g00) - a constant region is sampled exactly
+ *   cons = true when c == NULL, else with cf = S(c), d = b + cf:  |d|^2 <= alpha (|b|^2 + |cf|^2) + beta
+ *   Vs   = min of V_prev over the (up to four) neighbours of pc whose bilinear weight is non-zero
+ *   F    = b + S(F_prev);   V = inb and cons and Vs > 1/2  (written as 1 / 0)
+ *   mask = V ? bilinear sample (border clamp) of M at (x, y) + F, clamped to the frame : fill
+ * N chains run in one launch (both directions of a key frame inside the video); all tensors are contiguous fp32.
+ * INSV2V_EINVAL: a NULL descriptor or pointer other than c; N <= 0; H <= 1 or W <= 1; alpha or beta negative or not finite; a NaN fill;
+ * N*2*H*W beyond the grid; an output that overlaps an input or another output (a pixel reads neighbours that other threads write).
+ */
+typedef struct insv2v_masktrack_desc {
+    const float* f_prev;   /* [N,2,H,W] flow to the key frame of the chain's previous frame */
+    const float* v_prev;   /* [N,H,W]   its validity, 0 or 1 */
+    const float* b;        /* [N,2,H,W] flow on frame t into t' */
+    const float* c;        /* [N,2,H,W] flow on frame t' into t, or NULL: no forward-backward consistency check */
+    const float* m;        /* [N,H,W]   the key frame's mask */
+    float* f_out;          /* [N,2,H,W] */
+    float* v_out;          /* [N,H,W]   */
+    float* mask_out;       /* [N,H,W]   */
+    int32_t N, H, W;
+    float alpha, beta, fill;
+} insv2v_masktrack_desc;
+int insv2v_mask_track_step(const insv2v_masktrack_desc* d, insv2v_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -143,6 +143,12 @@ class ClipPreprocessDesc(C.Structure):
                 ("in_scale", c_f32), ("in_shift", c_f32), ("mean", c_f32 * 3), ("std", c_f32 * 3)]
 
 
+class MaskTrackDesc(C.Structure):
+    """insv2v_masktrack_desc: one step of the key-frame mask chain (csrc/masktrack.hip)."""
+    _fields_ = [("f_prev", c_p), ("v_prev", c_p), ("b", c_p), ("c", c_p), ("m", c_p), ("f_out", c_p), ("v_out", c_p), ("mask_out", c_p),
+                ("N", c_i32), ("H", c_i32), ("W", c_i32), ("alpha", c_f32), ("beta", c_f32), ("fill", c_f32)]
+
+
 # name -> (restype, argtypes); mirrors include/insv2v_hip.h one to one.
 SIGNATURES = {
     "insv2v_abi_version": (c_i32, []),
@@ -208,6 +214,7 @@ SIGNATURES = {
     "insv2v_eps_absdiff_accum": (c_i32, [c_p, c_p, c_i32, c_i32, c_i32, c_i64, c_f32, c_i32, c_p]),
     "insv2v_automask_workspace_bytes": (c_i64, [c_i32, c_i32, c_i32]),
     "insv2v_automask_finish": (c_i32, [c_p, c_p, c_p, c_p, c_p, c_i64, c_i32, c_i32, c_i32, c_f32, c_f32, c_i32, c_i32, c_p]),
+    "insv2v_mask_track_step": (c_i32, [C.POINTER(MaskTrackDesc), c_p]),
 }
 
 _lib = None

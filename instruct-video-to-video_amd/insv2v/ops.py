@@ -11,7 +11,7 @@ import torch
 
 from . import _lib
 from .rng import as_int64
-from ._lib import GemmDesc, GroupNormDesc, LayerNormDesc, AttentionDesc, StepDesc, MStepDesc, MaskStepDesc, FfnDesc, RowLinDesc, TattnDesc, XattnDesc, WinogradInDesc, WinogradOutDesc, check
+from ._lib import GemmDesc, GroupNormDesc, LayerNormDesc, AttentionDesc, StepDesc, MStepDesc, MaskStepDesc, MaskTrackDesc, FfnDesc, RowLinDesc, TattnDesc, XattnDesc, WinogradInDesc, WinogradOutDesc, check
 
 ACT_NONE, ACT_SILU, ACT_GEGLU, ACT_QUICK_GELU = 0, 1, 2, 3
 ACT_RELU, ACT_SIGMOID, ACT_TANH = 4, 5, 6   # the optical-flow network's (insv2v/raft.py)
@@ -824,6 +824,34 @@ def composite(edited, original, mask, out=None):
     N, _, H, W = edited.shape
     check(lib.insv2v_composite(edited.data_ptr(), original.data_ptr(), mask.data_ptr(), out.data_ptr(), N, H, W, _stream()), "insv2v_composite")
     return out
+
+
+def mask_track_step(f_prev, v_prev, b, c, m, *, alpha=0.01, beta=0.5, fill=0.0, out=None):
+    """One step of the key-frame mask chain (insv2v_mask_track_step; DESIGN.md section 19, tests/masktrack_ref.py is the definition):
+    fp32 ``f_prev`` [N,2,H,W] / ``v_prev`` [N,H,W] of the chain's previous frame, ``b`` [N,2,H,W] the flow on this frame into the previous
+    one, ``c`` the opposite flow or None (no consistency check), ``m`` [N,H,W] the key mask -> (F [N,2,H,W], V [N,H,W], mask [N,H,W]).
+    ``out``: that triple, preallocated; the entry refuses outputs that overlap an input or one another."""
+    lib = _lib.load()
+    N, _, H, W = b.shape if torch.is_tensor(b) and b.dim() == 4 else (0, 0, 0, 0)
+    for name, t, shape in (("f_prev", f_prev, (N, 2, H, W)), ("v_prev", v_prev, (N, H, W)), ("b", b, (N, 2, H, W)), ("c", c, (N, 2, H, W)),
+                           ("m", m, (N, H, W))):
+        if t is None and name == "c":
+            continue
+        _req(t, torch.float32, "mask_track_step." + name)
+        if tuple(t.shape) != shape or not t.is_contiguous():
+            raise _lib.HipKernelError(f"mask_track_step: {name} {tuple(t.shape)} must be a contiguous {shape}")
+    if out is None:
+        out = (torch.empty_like(b), torch.empty_like(v_prev), torch.empty_like(v_prev))
+    for name, t, shape in zip(("F", "V", "mask"), out, ((N, 2, H, W), (N, H, W), (N, H, W))):
+        _req(t, torch.float32, "mask_track_step.out." + name)
+        if tuple(t.shape) != shape or not t.is_contiguous():
+            raise _lib.HipKernelError(f"mask_track_step: out {name} {tuple(t.shape)} must be a contiguous {shape}")
+    d = MaskTrackDesc()
+    d.f_prev, d.v_prev, d.b, d.c, d.m = f_prev.data_ptr(), v_prev.data_ptr(), b.data_ptr(), _ptr(c), m.data_ptr()
+    d.f_out, d.v_out, d.mask_out = (t.data_ptr() for t in out)
+    d.N, d.H, d.W, d.alpha, d.beta, d.fill = N, H, W, alpha, beta, fill
+    check(lib.insv2v_mask_track_step(_byref(d), _stream()), "insv2v_mask_track_step")
+    return tuple(out)
 
 
 def add_noise(z, noise, ka, kb):

@@ -11,6 +11,10 @@ the HIP kernels with the BPE vocabulary from ``--tokenizer-dir``), writing the r
 
 With ``--score-ckpt FILE --score-out FILE.json`` (or ``--score-synthetic`` next to ``--synthetic``) every unit is scored after its edit
 with CLIP on the HIP kernels (``insv2v/clip_score.py``: the reference's ``ClipSimilarity`` numbers, text alignment, frame consistency).
+
+Masks: drawn per frame or still (``mask=``, the "mask" entry of a ``--units`` file, ``--mask-file``), estimated from the prompt
+(``mask="auto"``, ``--auto-mask``), or drawn on one frame and tracked through the video with optical flow (``mask_key=``, ``--mask-key``:
+``insv2v/mask_track.py``).
 """
 import argparse
 import os
@@ -51,12 +55,21 @@ MASK_MODES = ("mean", "max")
 AUTO_MASK_KEYS = ("n_maps", "mask_strength", "clamp_ratio", "threshold", "smooth", "dilate", "frames_in_batch", "noises")
 
 
-def check_edit_args(frames_shape, mask=None, strength=1.0, mask_mode="max", auto_mask=None):
+MASK_TRACK_KEYS = ("occlusion", "alpha", "beta", "fill")
+
+
+def check_edit_args(frames_shape, mask=None, strength=1.0, mask_mode="max", auto_mask=None, mask_key=None, mask_flows=None, mask_track=None):
     """Host-side check of the localized / partial edit controls (nothing is launched): ``strength`` in (0, 1], ``mask_mode`` "mean" or
     "max", ``mask`` a floating-point [1,T,H,W] or [1,1,H,W] tensor for frames [1,T,3,H,W] with H and W multiples of 8 - or the string
     "auto" (the mask is estimated from the prompt, ``InferenceIP2PVideo.estimate_mask``), then optionally with ``auto_mask``, a dict of
-    that method's keywords (``AUTO_MASK_KEYS``)."""
+    that method's keywords (``AUTO_MASK_KEYS``).  ``mask_key`` (a frame index: the mask, then a [1,1,H,W] tensor, is drawn on that frame
+    and tracked through the video, ``insv2v/mask_track.py``) optionally with ``mask_flows``, a dict(fwd=, bwd=) of [T-1,2,H,W] flows, and
+    ``mask_track``, a dict of ``propagate_mask``'s keywords (``MASK_TRACK_KEYS``)."""
     strength_to_start(strength, 1)
+    if mask_key is None and (mask_flows is not None or mask_track is not None):
+        raise ValueError("mask_flows / mask_track belong to a tracked mask: pass mask_key=, the frame the mask is drawn on, with them")
+    if mask_key is not None:
+        _check_track_args(frames_shape, mask, mask_key, mask_flows, mask_track)
     if mask_mode not in MASK_MODES:
         raise ValueError(f"mask_mode {mask_mode!r} is neither 'mean' nor 'max'")
     if auto_mask is not None and not (isinstance(mask, str) and mask == "auto"):
@@ -85,6 +98,31 @@ def check_edit_args(frames_shape, mask=None, strength=1.0, mask_mode="max", auto
         raise ValueError(f"mask {tuple(mask.shape)} must be [1,{T},{H},{W}] or [1,1,{H},{W}] (image resolution) for frames {tuple(frames_shape)}")
     if H % 8 or W % 8:
         raise ValueError(f"a mask needs frame sizes that are multiples of 8 (one latent cell per 8x8 pixels), not {H}x{W}")
+
+
+def _check_track_args(frames_shape, mask, mask_key, mask_flows, mask_track):
+    """The ``mask_key`` part of ``check_edit_args``."""
+    from .mask_track import check_track_args
+    T, H, W = frames_shape[1], frames_shape[3], frames_shape[4]
+    if isinstance(mask, str) or not torch.is_tensor(mask) or mask.dim() != 4 or tuple(mask.shape[:2]) != (1, 1):
+        raise ValueError(f"mask_key tracks a mask drawn on one frame: mask must be a [1,1,{H},{W}] tensor (not \"auto\", not one mask per frame)")
+    if isinstance(mask_key, bool) or not isinstance(mask_key, int) or not 0 <= mask_key < T:
+        raise ValueError(f"mask_key {mask_key!r} is not a frame index of a video of {T} frames")
+    track = {} if mask_track is None else mask_track
+    if not isinstance(track, dict) or set(track) - set(MASK_TRACK_KEYS):
+        raise ValueError(f"mask_track (the parameters of a tracked mask) must be a dict with keys among {MASK_TRACK_KEYS}, got {mask_track!r}")
+    try:
+        check_track_args(**track)
+    except ValueError as e:
+        raise ValueError(f"mask_track (the parameters of a tracked mask): {e}") from None
+    if mask_flows is not None:
+        if not isinstance(mask_flows, dict) or set(mask_flows) - {"fwd", "bwd"} or not mask_flows:
+            raise ValueError(f"mask_flows must be a dict(fwd=, bwd=) of [{T - 1},2,{H},{W}] flows")
+        for k, f in mask_flows.items():
+            if f is not None and (not torch.is_tensor(f) or tuple(f.shape) != (T - 1, 2, H, W)):
+                raise ValueError(f"mask_flows[{k!r}] {tuple(getattr(f, 'shape', ()))} must be [{T - 1},2,{H},{W}] for frames {tuple(frames_shape)}")
+        if track.get("occlusion", True) and T > 1 and (mask_flows.get("fwd") is None or mask_flows.get("bwd") is None):
+            raise ValueError("mask_flows: the occlusion check of a tracked mask needs both fwd and bwd (or mask_track=dict(occlusion=False))")
 
 
 def _start_time(inf_pipe, strength):
@@ -149,6 +187,23 @@ def _estimate_mask(model, inf_pipe, z, cond, text_cond, text_uncond, frames_in_b
     return inf_pipe.estimate_mask(z, text_cond, text_uncond, cond, **kw, **_seeded(seed, unit))
 
 
+def _track_mask(inf_pipe, frames, mask, mask_key, mask_flows, flow_estimator, mask_track, dev):
+    """``mask_key=``: the unit's mask, tracked ONCE from the whole video in launches of its own, before its first window
+    (``mask_track.propagate_mask``) -> its result dict; ``["mask"]`` [1,T,H,W] then goes through ``_EditPlan`` like a user's."""
+    from .mask_track import pair_flows, propagate_mask
+    track = dict(mask_track or {})
+    T = frames.shape[1]
+    if mask_flows is None and T > 1:
+        est = flow_estimator if flow_estimator is not None else getattr(inf_pipe, "flow_estimator", None)
+        if est is None:
+            raise RuntimeError("tracked mask (mask_key=) without a flow source: pass mask_flows= or flow_estimator=, or build the pipe with flow_estimator=")
+        mask_flows = pair_flows(frames, est, both=track.get("occlusion", True), key=mask_key)
+    if T == 1:   # nothing to track: no flow is needed, none is launched
+        mask_flows = {k: torch.zeros((0, 2, *frames.shape[-2:]), device=dev) for k in ("fwd", "bwd")}
+    flows = {k: (None if mask_flows.get(k) is None else mask_flows[k].to(device=dev, dtype=torch.float32)) for k in ("fwd", "bwd")}
+    return propagate_mask(mask.to(device=dev), mask_key, flows["fwd"], flows["bwd"], **track)
+
+
 def _result(image, latent, est, return_latent, return_mask):
     out = (image,) + ((latent,) if return_latent else ()) + ((est,) if return_mask else ())
     return out if len(out) > 1 else image
@@ -157,7 +212,8 @@ def _result(image, latent, est, return_latent, return_mask):
 @torch.no_grad()
 def edit_video(model, inf_pipe, frames, text_cond, text_uncond, text_cfg=7.5, video_cfg=1.8, frames_in_batch=16,
                num_ref_frames=4, init_noises=None, enc_noise=None, flows_per_window=None, return_latent=False, cond=None,
-               seed=None, unit=0, mask=None, strength=1.0, mask_mode="max", auto_mask=None, return_mask=False):
+               seed=None, unit=0, mask=None, strength=1.0, mask_mode="max", auto_mask=None, return_mask=False,
+               mask_key=None, mask_flows=None, flow_estimator=None, mask_track=None):
     """frames [1,T,3,H,W] in [-1,1] -> edited frames [1,T,3,H,W] clipped to [-1,1].
 
     ``seed`` (default None: every draw comes from the global torch generators, as before) makes the edit reproducible: the posterior
@@ -185,14 +241,24 @@ def edit_video(model, inf_pipe, frames, text_cond, text_uncond, text_cfg=7.5, vi
     over every 8x8 cell, so ``mask_mode`` has no effect on it).  ``auto_mask``: a dict of the estimator's keywords (``AUTO_MASK_KEYS``;
     default: its defaults, chunks of ``frames_in_batch`` frames); with ``seed`` the estimate's noise comes from the unit's MASK streams.
     ``return_mask=True`` appends the estimator's result dict (``raw``, ``soft``, ``mask_latent``, ``mask``; None without ``mask="auto"``)
-    to the returned tuple."""
-    check_edit_args(frames.shape, mask, strength, mask_mode, auto_mask)
+    to the returned tuple.
+
+    ``mask_key=k``: ``mask`` ([1,1,H,W]) is drawn on frame k only and follows the motion: the adjacent-frame flows
+    - ``mask_flows``, a dict(fwd=, bwd=) of [T-1,2,H,W] flows, else computed by ``flow_estimator`` (default: the pipe's own) with
+    ``mask_track.pair_flows`` - are chained into the flow from every frame to frame k and the mask is sampled once per frame
+    (``mask_track.propagate_mask``; ``mask_track``: a dict of its keywords, ``MASK_TRACK_KEYS``).  Computed once per unit from the whole
+    video, before the first window; from there it is a user's [1,T,H,W] mask.  ``return_mask=True`` then returns ``propagate_mask``'s
+    dict (``mask``, ``valid``, ``flow_to_key``).  Without ``mask_key`` nothing of this runs."""
+    check_edit_args(frames.shape, mask, strength, mask_mode, auto_mask, mask_key, mask_flows, mask_track)
     dev = model.unet.device
+    est = None
+    if mask_key is not None:
+        est = _track_mask(inf_pipe, frames, mask, mask_key, mask_flows, flow_estimator, mask_track, dev)
+        mask = est["mask"]
     z = None
     if cond is None:
         z = model.encode_image_to_latent(frames, enc_noise, **_seeded(seed, unit))
         cond = z / model.scale_factor
-    est = None
     if isinstance(mask, str):   # "auto" (check_edit_args)
         est = _estimate_mask(model, inf_pipe, z, cond, text_cond, text_uncond, frames_in_batch, auto_mask, seed, unit)
         mask = est["mask"]
@@ -237,7 +303,8 @@ def edit_video(model, inf_pipe, frames, text_cond, text_uncond, text_cfg=7.5, vi
 
 
 @torch.no_grad()
-def edit_videos(model, inf_pipe, units, frames_in_batch=16, num_ref_frames=4, return_latent=False, seed=None, max_clips=None, return_mask=False):
+def edit_videos(model, inf_pipe, units, frames_in_batch=16, num_ref_frames=4, return_latent=False, seed=None, max_clips=None, return_mask=False,
+                flow_estimator=None):
     """Several independent units at once - the throughput form of ``edit_video`` (the reference's unit loop offers them naturally: four
     prompts per video, insv2v_run_loveu_tgve.py:83,101): window k of ALL units runs as one stacked launch chain
     (``InferenceIP2PVideo.run_stacked``: B = 3 x units in every UNet launch, weights read once, every launch fills the chip), windows
@@ -254,18 +321,24 @@ def edit_videos(model, inf_pipe, units, frames_in_batch=16, num_ref_frames=4, re
     of one call must share the number of executed steps (a stack shares ``start_time``), so strengths that round to different step
     counts raise ValueError.  A unit may also carry ``mask="auto"`` (and ``auto_mask``): its mask is estimated alone, in launches of its
     own, before the stacked windows start - so it is bit for bit the mask ``edit_video`` estimates for that unit.  ``return_mask``: as
-    for ``edit_video``, per unit."""
+    for ``edit_video``, per unit.  A unit may carry ``mask_key`` (and ``mask_flows``, ``mask_track``) as for ``edit_video``: its mask is
+    tracked alone, before the stacked windows start, bit for bit as ``edit_video`` tracks it; ``flow_estimator`` is the flow source of
+    the units without ``mask_flows`` (default: the pipe's own).  Tracked, drawn, auto and unmasked units stack together."""
     if len(units) == 0:
         return []
     for u in units:
-        check_edit_args(u["frames"].shape, u.get("mask"), u.get("strength", 1.0), u.get("mask_mode", "max"), u.get("auto_mask"))
+        check_edit_args(u["frames"].shape, u.get("mask"), u.get("strength", 1.0), u.get("mask_mode", "max"), u.get("auto_mask"),
+                        u.get("mask_key"), u.get("mask_flows"), u.get("mask_track"))
     if len({_start_time(inf_pipe, u.get("strength", 1.0)) for u in units}) > 1:
         raise ValueError("edit_videos: the units of one call must share the number of executed steps (strength); edit the others separately")
     wants_flow = hasattr(inf_pipe, "obtain_flow_batched")
     ids = [u.get("unit", j) for j, u in enumerate(units)]
     if len(units) == 1:
-        keys = ("text_cfg", "video_cfg", "init_noises", "enc_noise", "cond", "flows_per_window", "mask", "strength", "mask_mode", "auto_mask")
+        keys = ("text_cfg", "video_cfg", "init_noises", "enc_noise", "cond", "flows_per_window", "mask", "strength", "mask_mode", "auto_mask",
+                "mask_key", "mask_flows", "mask_track")
         more = {"return_mask": True} if return_mask else {}   # (a plain call carries no new keyword)
+        if flow_estimator is not None:
+            more["flow_estimator"] = flow_estimator
         return [edit_video(model, inf_pipe, u["frames"], u["text_cond"], u["text_uncond"], frames_in_batch=frames_in_batch,
                            num_ref_frames=num_ref_frames, return_latent=return_latent, seed=seed, unit=ids[0], **more,
                            **{k: u[k] for k in keys if k in u}) for u in units]
@@ -282,6 +355,9 @@ def edit_videos(model, inf_pipe, units, frames_in_batch=16, num_ref_frames=4, re
             cond = z / model.scale_factor
         conds, refs = split_batch(cond, frames_in_batch, num_ref_frames)
         mask, est = u.get("mask"), None
+        if u.get("mask_key") is not None:   # tracked here, alone, before the first stacked window of any unit
+            est = _track_mask(inf_pipe, u["frames"], mask, u["mask_key"], u.get("mask_flows"), flow_estimator, u.get("mask_track"), dev)
+            mask = est["mask"]
         if isinstance(mask, str):   # "auto": estimated here, alone, before the first stacked window of any unit
             est = _estimate_mask(model, inf_pipe, z, cond, u["text_cond"], u["text_uncond"], frames_in_batch, u.get("auto_mask"), seed, uid)
             mask = est["mask"]
@@ -381,7 +457,16 @@ def build_parser():
     p.add_argument("--auto-mask-strength", type=float, default=0.5, help="in (0, 1]: the noise level of those copies, as --strength")
     p.add_argument("--auto-mask-threshold", type=float, default=0.5, help="in (0, 1): a cell is edited where the normalised map exceeds it")
     p.add_argument("--auto-mask-dilate", type=int, default=1, help="latent cells the thresholded mask is grown by")
-    p.add_argument("--mask-out", type=str, default=None, help=".pt file for the estimated masks: {unit id: {mask_latent, soft}} (with --auto-mask)")
+    p.add_argument("--mask-out", type=str, default=None,
+                   help=".pt file for the masks this run computed: {unit id: {mask_latent, soft}} with --auto-mask, {unit id: {mask, valid}} with --mask-key")
+    p.add_argument("--mask-file", type=str, default=None,
+                   help=".pt file with drawn masks: {unit id or video name: tensor [1,1,H,W] or [1,T,H,W]} (image resolution; units it does not "
+                        "name are edited whole)")
+    p.add_argument("--mask-key", type=int, default=None,
+                   help="the frame the masks are drawn on ([1,1,H,W] each): they follow the motion through the video (insv2v/mask_track.py); the "
+                        "flows come from the estimator of --raft-ckpt (--synthetic: key-hashed weights)")
+    p.add_argument("--mask-no-occlusion", action="store_true",
+                   help="with --mask-key: no forward-backward consistency check (half the flow pairs; occluded pixels keep a traced mask value)")
     p.add_argument("--raft-ckpt", type=str, default=None,
                    help="torchvision raft_large checkpoint (state dict) for --with_optical_flow: the estimator runs on the HIP kernels")
     p.add_argument("--flows", type=str, default=None,
@@ -420,8 +505,22 @@ def check_args(args):
             raise SystemExit(f"--auto-mask-maps / --auto-mask-strength / --auto-mask-threshold / --auto-mask-dilate: {e}")
     if getattr(args, "auto_mask", False) and getattr(args, "synthetic_mask", False):
         raise SystemExit("--auto-mask and --synthetic-mask are two masks: pass one")
-    if getattr(args, "mask_out", None) and not getattr(args, "auto_mask", False):
-        raise SystemExit("--mask-out holds the estimated masks: it needs --auto-mask")
+    mask_key, mask_file = getattr(args, "mask_key", None), getattr(args, "mask_file", None)
+    if getattr(args, "mask_out", None) and not getattr(args, "auto_mask", False) and mask_key is None:
+        raise SystemExit("--mask-out holds the masks a run computes: it needs --auto-mask or --mask-key")
+    if mask_file and (getattr(args, "auto_mask", False) or getattr(args, "synthetic_mask", False)):
+        raise SystemExit("--mask-file next to --auto-mask / --synthetic-mask are two masks: pass one")
+    if mask_key is not None:
+        if getattr(args, "auto_mask", False):
+            raise SystemExit("--mask-key tracks a drawn mask and --auto-mask estimates one per frame: pass one")
+        if mask_key < 0:
+            raise SystemExit(f"--mask-key must be a frame index, not {mask_key}")
+        if not (mask_file or getattr(args, "synthetic_mask", False) or args.units):
+            raise SystemExit("--mask-key needs a mask to track: --mask-file FILE.pt, the \"mask\" entry of a --units file, or --synthetic-mask")
+        if not (args.raft_ckpt or args.synthetic):
+            raise SystemExit("--mask-key needs --raft-ckpt FILE (torchvision raft_large weights): the flows the mask follows come from that estimator")
+    elif getattr(args, "mask_no_occlusion", False):
+        raise SystemExit("--mask-no-occlusion is a parameter of --mask-key")
     if args.flows and args.units is None and not args.synthetic:
         raise SystemExit("--flows is supported with --units / --synthetic (flows are indexed by unit)")
     score_synth, score_ckpt, score_out = (getattr(args, k, None) for k in ("score_synthetic", "score_ckpt", "score_out"))
@@ -479,8 +578,46 @@ def auto_mask_unit(args, data=None):
     return dict(mask="auto", auto_mask=auto_mask_kwargs(args))
 
 
+def mask_track_unit(args):
+    """What --mask-key adds to every unit that has a mask (nothing without it)."""
+    if getattr(args, "mask_key", None) is None:
+        return {}
+    return dict(mask_key=args.mask_key, mask_track=dict(occlusion=not getattr(args, "mask_no_occlusion", False)))
+
+
+def load_mask_file(args):
+    """{unit id or video name: mask tensor} of --mask-file ({} without it)."""
+    if not getattr(args, "mask_file", None):
+        return {}
+    masks = torch.load(args.mask_file, map_location="cpu")
+    if not isinstance(masks, dict) or not all(torch.is_tensor(m) and m.dim() == 4 and m.shape[0] == 1 for m in masks.values()):
+        raise SystemExit("--mask-file must hold {unit id or video name: tensor [1,1,H,W] or [1,T,H,W]}")
+    return masks
+
+
+def build_flow_estimator(args, device):
+    """The CLI's flow estimator of --mask-key (None without it): RAFT on the HIP kernels with the weights of --raft-ckpt, key-hashed
+    weights in a --synthetic run."""
+    if getattr(args, "mask_key", None) is None:
+        return None
+    from .raft import RAFTFlow
+    if args.raft_ckpt:
+        return RAFTFlow(device).load_state_dict(torch.load(args.raft_ckpt, map_location="cpu"))
+    from . import synth, shapes
+    return RAFTFlow(device, synth.synth_raft_state_dict(shapes.raft_shapes()))
+
+
 def write_masks(path, records, rank=0, world=1):
-    """{unit id: {"mask_latent": [T,h,w], "soft": [T,h,w]}} of this rank's units (with several ranks each writes its own FILE.rankR.pt)."""
+    """{unit id: {"mask_latent": [T,h,w], "soft": [T,h,w]}} (estimated, --auto-mask) or {unit id: {"mask": [T,H,W], "valid": [T,H,W]}}
+    (tracked, --mask-key) of this rank's units (with several ranks each writes its own FILE.rankR.pt)."""
+    records = {u: est for u, est in records.items() if est is not None}   # (a unit the mask file does not name has none)
+    if any("valid" in est for est in records.values()):
+        if world > 1:
+            root, ext = os.path.splitext(path)
+            path = f"{root}.rank{rank}{ext}"
+        os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
+        torch.save({int(u): {"mask": est["mask"][0].cpu(), "valid": est["valid"].cpu()} for u, est in sorted(records.items())}, path)
+        return
     if world > 1:
         root, ext = os.path.splitext(path)
         path = f"{root}.rank{rank}{ext}"
@@ -522,7 +659,9 @@ def run_dataset(args, model, pipe, rank=0, world=1, scorer=None):
     kinds = ("style", "object", "background", "multiple")
     records = []
     auto = auto_mask_unit(args)
-    want_masks = {"return_mask": True} if auto and getattr(args, "mask_out", None) else {}   # (a plain run carries no new keyword)
+    track, drawn = mask_track_unit(args), load_mask_file(args)   # drawn masks are named by video here
+    more = {"flow_estimator": build_flow_estimator(args, model.unet.device)} if track else {}
+    want_masks = {"return_mask": True} if (auto or track) and getattr(args, "mask_out", None) else {}   # (a plain run carries no new keyword)
     masks = {}
     for ci, (video_id, text_cfg, video_cfg, num_frames, image_size) in enumerate(combos):
         if ci % world != rank:
@@ -543,12 +682,14 @@ def run_dataset(args, model, pipe, rank=0, world=1, scorer=None):
                 continue
             todo.append((gif_path, image_dir, dict(frames=frames, text_cond=model.encode_text([prompt]), text_uncond=text_uncond,
                                                    text_cfg=text_cfg, video_cfg=video_cfg, cond=cond, unit=4 * ci + kinds.index(key),
-                                                   strength=getattr(args, "strength", 1.0), **auto), prompt))
+                                                   strength=getattr(args, "strength", 1.0), **auto,
+                                                   **(dict(mask=drawn[batch["video_name"]], mask_mode=getattr(args, "mask_mode", "max"),
+                                                           **track) if batch["video_name"] in drawn else {})), prompt))
         # the four prompts of a video share the conditioning latent and the window plan: one stacked launch chain per window (B = 12)
         if getattr(args, "no_stack", False):
-            edits = [edit_videos(model, pipe, [u], seed=seed, **want_masks)[0] for _, _, u, _ in todo]
+            edits = [edit_videos(model, pipe, [u], seed=seed, **want_masks, **more)[0] for _, _, u, _ in todo]
         else:
-            edits = edit_videos(model, pipe, [u for _, _, u, _ in todo], seed=seed, max_clips=getattr(args, "max_stack", None), **want_masks)
+            edits = edit_videos(model, pipe, [u for _, _, u, _ in todo], seed=seed, max_clips=getattr(args, "max_stack", None), **want_masks, **more)
         for (gif_path, image_dir, u, prompt), edited in zip(todo, edits):
             if want_masks:
                 edited, masks[u["unit"]] = edited
@@ -627,10 +768,19 @@ def main(argv=None):
     flows = torch.load(args.flows, map_location="cpu") if args.flows else None
     item_shape = tuple(data["frames"].shape[1:])  # a rank without units still takes part in the all_gather
     auto = auto_mask_unit(args, data)   # (refuses --auto-mask next to a "mask" entry of the file)
-    want_masks = {"return_mask": True} if auto and args.mask_out else {}
+    track, drawn = mask_track_unit(args), load_mask_file(args)   # drawn masks are named by unit here
+    if drawn and data.get("mask") is not None:
+        raise SystemExit("--mask-file next to the \"mask\" entry of the --units file are two masks: pass one")
+    if track and not drawn and data.get("mask") is None:
+        raise SystemExit("--mask-key needs a mask to track: --mask-file FILE.pt, the \"mask\" entry of a --units file, or --synthetic-mask")
+    more = {"flow_estimator": build_flow_estimator(args, f"cuda:{local}")} if track else {}
+    want_masks = {"return_mask": True} if (auto or track) and args.mask_out else {}
     est_masks = {}
     masks = data.get("mask")   # optional [n,T,H,W] / [n,1,H,W]
-    edit = lambda i: dict(dict(mask=masks[i:i + 1] if masks is not None else None, strength=args.strength, mask_mode=args.mask_mode), **auto)
+
+    def edit(i):
+        m = masks[i:i + 1] if masks is not None else drawn.get(i)
+        return dict(dict(mask=m, strength=args.strength, mask_mode=args.mask_mode), **auto, **(track if m is not None else {}))
     scorer = build_scorer(args, f"cuda:{local}", tok)
     records = []
     outs = []
@@ -641,7 +791,7 @@ def main(argv=None):
         if args.no_stack:
             local_out = [edit_video(model, pipe, data["frames"][i:i + 1], data["text_cond"][i:i + 1], data["text_uncond"],
                                     text_cfg, video_cfg, flows_per_window=flows[i] if flows is not None else None,
-                                    seed=args.seed, unit=ci * n + i, **edit(i), **want_masks) for i in mine]
+                                    seed=args.seed, unit=ci * n + i, **edit(i), **want_masks, **more) for i in mine]
         else:   # a rank's units as stacked launch chains (run_stacked caps the stack at what the kernels' operand window allows)
             from .inference import max_clips_in_flight
             T, S = data["frames"].shape[1], data["frames"].shape[-1]
@@ -651,7 +801,7 @@ def main(argv=None):
                 local_out += edit_videos(model, pipe, [dict(frames=data["frames"][i:i + 1], text_cond=data["text_cond"][i:i + 1],
                                                             text_uncond=data["text_uncond"], text_cfg=text_cfg, video_cfg=video_cfg, unit=ci * n + i, **edit(i),
                                                             **({"flows_per_window": flows[i]} if flows is not None else {}))
-                                                       for i in mine[g:g + cap]], seed=args.seed, max_clips=args.max_stack, **want_masks)
+                                                       for i in mine[g:g + cap]], seed=args.seed, max_clips=args.max_stack, **want_masks, **more)
         if want_masks:
             for i, (_, est) in zip(mine, local_out):
                 est_masks[ci * n + i] = est
