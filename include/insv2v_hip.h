@@ -51,7 +51,8 @@ typedef void* insv2v_stream_t; /* hipStream_t */
  * ABI 14: seeded noise - insv2v_randn, insv2v_posterior_sample_seeded and the noise_seed / noise_stream / noise_on fields of
  * insv2v_step_desc (section "seeded noise" below holds the stream definition, which is part of this contract).
  * ABI 15: insv2v_groupnorm_plan (an addition: no existing struct or entry changes); likewise the CLIP scoring entries
- * (insv2v_clip_preprocess, insv2v_clip_scores, insv2v_l2_normalize), added without a bump. */
+ * (insv2v_clip_preprocess, insv2v_clip_scores, insv2v_l2_normalize) and the pixel-space scores (insv2v_warp_error,
+ * insv2v_frame_fidelity and their workspace queries), added without a bump. */
 int insv2v_abi_version(void);
 /* One-time per-process setup (kernel attributes). Safe to call repeatedly. */
 int insv2v_init(void);
@@ -931,6 +932,81 @@ typedef struct insv2v_masktrack_desc {
     float alpha, beta, fill;
 } insv2v_masktrack_desc;
 int insv2v_mask_track_step(const insv2v_masktrack_desc* d, insv2v_stream_t stream);
+
+/*
+ * ---- scoring an edit in pixel space (additions to ABI 15: no existing struct or entry changes) ------------------------------------------
+ * The flow warp error of a video (does the edit flicker?) and the per-frame squared error and SSIM between two videos (did the edit leave
+ * alone what it should?): csrc/pixel_score.hip; tests/pixel_score_ref.py restates both definitions in float64.
+ *
+ * Frames are [T,3,H,W] views: fp16, or fp32 with fp32 != 0; element strides for frame, channel and row (all >= 0, row stride >= W), x
+ * contiguous - a crop of a larger tensor is a valid operand.  A value is mapped as it is read: v = clamp(x * scale + shift, 0, 1)
+ * (0.5, 0.5 for frames in [-1, 1]), so every metric is on [0, 1] data (data_range 1).
+ * Reductions have two stages in a fixed order: every workgroup writes its partial sums (fp64) to the caller's workspace, a finalize
+ * launch adds them in index order in fp64.  No floating-point atomics: two calls give the same bits.  Nothing is allocated; the
+ * workspace (8-byte aligned) holds at least insv2v_*_workspace_bytes bytes.  Outputs are fp64 (8-byte aligned).
+ * Host-side conventions, decided by the caller from the sums: mse = sum / weight sum; PSNR = 10 log10(1 / mse), +inf for mse == 0; a
+ * region whose weight sum is 0 gives nan.
+ */
+typedef struct insv2v_frames_view {
+    const void* p;
+    int64_t stride_t, stride_c, stride_h;
+    int32_t fp32;
+    float scale, shift;
+} insv2v_frames_view;
+
+/* The T-1 adjacent pairs of one video A.  b = fwd[t] is defined on frame t and points into t+1 (the convention of insv2v_warp_image:
+ * sampling frame t+1 at x + b(x) gives frame t); c = bwd[t] is the opposite flow.  Per pixel x of frame t, with p, inb, the clamped
+ * point and the sample S(.) exactly as defined above for insv2v_mask_track_step (border clamp, lerps):
+ *   cons  = true when bwd == NULL, else with cf = S(c), d = b + cf:  |d|^2 <= alpha (|b|^2 + |cf|^2) + beta   (that entry's inequality)
+ *   valid = inb and cons
+ *   err   = (1/3) sum_c (A_t[c](x) - S(A_{t+1}[c]))^2    fp32: the three squares added in channel order, then divided by 3
+ * sums[t] = (sum valid w_t err, sum valid w_t, the count of valid pixels); w = the region weight of frame t, 1 when NULL.  The products
+ * w * err are formed and added in fp64.  err_map / valid_map (NULL = not written): err (0 where invalid) and valid as 1 / 0.
+ * INSV2V_EINVAL, nothing launched and no output touched: a NULL descriptor, frames, fwd, sums or workspace; T < 2; H <= 1 or W <= 1;
+ * alpha or beta negative or not finite; a negative stride or a row stride below W; a workspace that is too small or misaligned; T - 1
+ * above 65535 or a plane beyond the grid; an output (sums, maps, workspace) that overlaps an input or another output. */
+typedef struct insv2v_warp_error_desc {
+    insv2v_frames_view a;
+    const float* fwd;      /* [T-1,2,H,W] contiguous */
+    const float* bwd;      /* [T-1,2,H,W] contiguous, or NULL: no consistency check */
+    const float* w;        /* [T,H,W] contiguous, values in [0,1], or NULL: 1 */
+    double* sums;          /* [T-1,3] */
+    float* err_map;        /* [T-1,H,W] or NULL */
+    float* valid_map;      /* [T-1,H,W] or NULL */
+    void* workspace;
+    int64_t workspace_bytes;
+    int32_t T, H, W;
+    float alpha, beta;
+} insv2v_warp_error_desc;
+/* Bytes of workspace for a video of T frames of H x W; INSV2V_EINVAL for a size the entry refuses. */
+int64_t insv2v_warp_error_workspace_bytes(int32_t T, int32_t H, int32_t W);
+int insv2v_warp_error(const insv2v_warp_error_desc* d, insv2v_stream_t stream);
+
+/* Source X against edit Y, frame by frame, one pass over the data.  sums[t] (INSV2V_FIDELITY_K fp64 values), w = the region weight
+ * (1 when NULL), se = (1/3) sum_c (x - y)^2 per pixel (fp32, as err above):
+ *   0 sum se    1 sum w se    2 sum (1-w) se    3 sum w    4 sum (1-w)            each accumulated separately, products in fp64: with a
+ *                                                                                  binary w and identical pixels outside, sum 2 is exactly 0
+ *   5 sum s     6 sum wc s    7 sum (1-wc) s    8 sum wc   9 sum (1-wc)           over the SSIM centres, wc = w at the window centre
+ * SSIM (Wang et al. 2004): Gaussian window of 11 taps, sigma 1.5, weights exp(-k^2 / 2 sigma^2), k = -5..5, normalised to sum 1,
+ * separable; the window stays inside the frame - centres 5 <= y <= H-6, 5 <= x <= W-6, no padding; C1 = 0.01^2, C2 = 0.03^2;
+ * population (co)variances sx2 = E[x^2] - mx^2, sxy = E[xy] - mx my; per channel
+ *   ((2 mx my + C1) (2 sxy + C2)) / ((mx^2 + my^2 + C1) (sx2 + sy2 + C2)),   s = the mean of the three channels at a centre.
+ * fp32: the moments are those of x - 1/2 and y - 1/2 (the variances do not change, their cancellation error shrinks), a row pass then a
+ * column pass, each a sum in tap order.
+ * INSV2V_EINVAL: as insv2v_warp_error (T < 1 in place of T < 2, no alpha / beta), and H < 11 or W < 11. */
+#define INSV2V_FIDELITY_K 10
+typedef struct insv2v_fidelity_desc {
+    insv2v_frames_view x, y;
+    const float* w;        /* [T,H,W] contiguous, values in [0,1], or NULL: 1 */
+    double* sums;          /* [T,INSV2V_FIDELITY_K] */
+    void* workspace;
+    int64_t workspace_bytes;
+    int32_t T, H, W;
+} insv2v_fidelity_desc;
+int64_t insv2v_frame_fidelity_workspace_bytes(int32_t T, int32_t H, int32_t W);
+int insv2v_frame_fidelity(const insv2v_fidelity_desc* d, insv2v_stream_t stream);
+/* The kernel's tile of SSIM centres (rows, columns): what the tests name their shapes from.  Returns 0. */
+int insv2v_frame_fidelity_tile(int32_t* rows, int32_t* cols);
 
 #ifdef __cplusplus
 }

@@ -2,32 +2,11 @@
 // the key frame, its validity and the tracked mask from a frame t' to its neighbour t.  tests/masktrack_ref.py restates the definition in
 // float64.  A gather over a few fp32 planes: launch-bound at video sizes, no matrix cores, nothing tuned beyond row-major access.
 #include "common.h"
+#include "flow_sample.h"
 #include <math.h>
 
-// Border-clamped bilinear sample at a point: the point is clamped to the frame, x0 = floor, x1 = min(x0 + 1, W - 1), the same in y.
-// (A NaN coordinate clamps to 0: fmaxf returns its other operand.  The integer clamp covers a W - 1 that fp32 rounds up.)
-// Evaluated as lerps - top + ay (bottom - top), top = g00 + ax (g01 - g00) - so a constant region is sampled exactly: a binary mask
-// stays exactly 0 / 1 away from its edges.  A tap's bilinear weight is non-zero iff its ax / ay factors are (ax, ay in [0, 1)).
-struct MtTaps {
-    int64_t o00, o01, o10, o11;
-    float ax, ay;
-};
-__device__ __forceinline__ MtTaps mt_taps(float px, float py, int H, int W) {
-    const float cx = fminf(fmaxf(px, 0.f), (float)(W - 1)), cy = fminf(fmaxf(py, 0.f), (float)(H - 1));
-    const float fx = floorf(cx), fy = floorf(cy);
-    const int x0 = min(max((int)fx, 0), W - 1), y0 = min(max((int)fy, 0), H - 1);
-    const int x1 = min(x0 + 1, W - 1), y1 = min(y0 + 1, H - 1);
-    MtTaps t;
-    t.ax = cx - fx, t.ay = cy - fy;
-    t.o00 = (int64_t)y0 * W + x0, t.o01 = (int64_t)y0 * W + x1, t.o10 = (int64_t)y1 * W + x0, t.o11 = (int64_t)y1 * W + x1;
-    return t;
-}
-__device__ __forceinline__ float mt_sample(const MtTaps& t, const float* __restrict__ g) {
-    const float g00 = g[t.o00], g01 = g[t.o01], g10 = g[t.o10], g11 = g[t.o11];
-    const float top = g00 + t.ax * (g01 - g00), bottom = g10 + t.ax * (g11 - g10);
-    return top + t.ay * (bottom - top);
-}
-
+// The border-clamped bilinear sample (mt_taps / mt_sample) and the consistency rule (mt_consistent) live in flow_sample.h, shared with
+// the flow warp error of pixel_score.hip.
 // One thread per pixel (n, y, x) of the N chains; consecutive threads walk a row, so b, c's centre and every store are coalesced.
 __global__ __launch_bounds__(256) void mask_track_step_kernel(const float* __restrict__ f_prev, const float* __restrict__ v_prev,
                                                               const float* __restrict__ b, const float* __restrict__ c,
@@ -46,8 +25,7 @@ __global__ __launch_bounds__(256) void mask_track_step_kernel(const float* __res
     bool cons = true;
     if (c) {
         const float cfx = mt_sample(t, c + n * 2 * plane), cfy = mt_sample(t, c + (n * 2 + 1) * plane);
-        const float dx = bx + cfx, dy = by + cfy;
-        cons = dx * dx + dy * dy <= alpha * ((bx * bx + by * by) + (cfx * cfx + cfy * cfy)) + beta;
+        cons = mt_consistent(bx, by, cfx, cfy, alpha, beta);
     }
     const float* vp = v_prev + n * plane;
     float vs = fminf(1.f, vp[t.o00]);

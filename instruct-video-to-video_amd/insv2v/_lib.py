@@ -149,6 +149,26 @@ class MaskTrackDesc(C.Structure):
                 ("N", c_i32), ("H", c_i32), ("W", c_i32), ("alpha", c_f32), ("beta", c_f32), ("fill", c_f32)]
 
 
+class FramesView(C.Structure):
+    """insv2v_frames_view: [T,3,H,W] fp16 / fp32 frames with explicit strides and the affine map applied as a value is read."""
+    _fields_ = [("p", c_p), ("stride_t", c_i64), ("stride_c", c_i64), ("stride_h", c_i64), ("fp32", c_i32), ("scale", c_f32), ("shift", c_f32)]
+
+
+class WarpErrorDesc(C.Structure):
+    """insv2v_warp_error_desc (csrc/pixel_score.hip)."""
+    _fields_ = [("a", FramesView), ("fwd", c_p), ("bwd", c_p), ("w", c_p), ("sums", c_p), ("err_map", c_p), ("valid_map", c_p),
+                ("workspace", c_p), ("workspace_bytes", c_i64), ("T", c_i32), ("H", c_i32), ("W", c_i32), ("alpha", c_f32), ("beta", c_f32)]
+
+
+FIDELITY_K = 10   # INSV2V_FIDELITY_K
+
+
+class FidelityDesc(C.Structure):
+    """insv2v_fidelity_desc (csrc/pixel_score.hip)."""
+    _fields_ = [("x", FramesView), ("y", FramesView), ("w", c_p), ("sums", c_p), ("workspace", c_p), ("workspace_bytes", c_i64),
+                ("T", c_i32), ("H", c_i32), ("W", c_i32)]
+
+
 # name -> (restype, argtypes); mirrors include/insv2v_hip.h one to one.
 SIGNATURES = {
     "insv2v_abi_version": (c_i32, []),
@@ -215,6 +235,11 @@ SIGNATURES = {
     "insv2v_automask_workspace_bytes": (c_i64, [c_i32, c_i32, c_i32]),
     "insv2v_automask_finish": (c_i32, [c_p, c_p, c_p, c_p, c_p, c_i64, c_i32, c_i32, c_i32, c_f32, c_f32, c_i32, c_i32, c_p]),
     "insv2v_mask_track_step": (c_i32, [C.POINTER(MaskTrackDesc), c_p]),
+    "insv2v_warp_error_workspace_bytes": (c_i64, [c_i32, c_i32, c_i32]),
+    "insv2v_warp_error": (c_i32, [C.POINTER(WarpErrorDesc), c_p]),
+    "insv2v_frame_fidelity_workspace_bytes": (c_i64, [c_i32, c_i32, c_i32]),
+    "insv2v_frame_fidelity": (c_i32, [C.POINTER(FidelityDesc), c_p]),
+    "insv2v_frame_fidelity_tile": (c_i32, [C.POINTER(c_i32), C.POINTER(c_i32)]),
 }
 
 _lib = None

@@ -1198,3 +1198,106 @@ def l2_normalize(x):
     check(lib.insv2v_l2_normalize(x.data_ptr(), int(x.dtype == torch.float32), x.stride(0), out.data_ptr(), out.stride(0), x.shape[0],
                                   x.shape[1], _stream()), "insv2v_l2_normalize")
     return out
+
+
+# ----------------------------------------------------------------------------- scoring an edit in pixel space (insv2v/pixel_score.py)
+FIDELITY_KEYS = ("se", "se_in", "se_out", "w_in", "w_out", "ssim", "ssim_in", "ssim_out", "wc_in", "wc_out")   # insv2v_frame_fidelity's sums
+
+
+def _frames_view(v, t, name, scale, shift):
+    """Fill an insv2v_frames_view from a [T,3,H,W] fp16 / fp32 CUDA tensor (any view whose rows are contiguous)."""
+    if not torch.is_tensor(t) or not t.is_cuda or t.dtype not in (torch.float16, torch.float32):
+        raise _lib.HipKernelError(f"{name}: expected a CUDA float16 / float32 tensor")
+    if t.dim() != 4 or t.shape[1] != 3 or (t.shape[3] > 1 and t.stride(3) != 1):
+        raise _lib.HipKernelError(f"{name}: {tuple(t.shape)} (strides {t.stride()}) must be [T,3,H,W] with contiguous rows")
+    v.p, v.fp32, v.scale, v.shift = t.data_ptr() or None, int(t.dtype == torch.float32), scale, shift
+    v.stride_t, v.stride_c, v.stride_h = t.stride(0), t.stride(1), t.stride(2)
+    return tuple(t.shape)
+
+
+def _plain(t, shape, name, dtype=torch.float32):
+    _req(t, dtype, name)
+    if tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise _lib.HipKernelError(f"{name}: {tuple(t.shape)} must be a contiguous {tuple(shape)}")
+    return t
+
+
+def _score_workspace(nbytes, device, workspace, name):
+    if nbytes <= 0:
+        raise _lib.HipKernelError(f"{name}: no workspace size for these frames")
+    if workspace is None:
+        workspace = torch.empty(nbytes // 8, device=device, dtype=torch.float64)
+    else:
+        _req(workspace, torch.float64, name + ".workspace")
+        if not workspace.is_contiguous():
+            raise _lib.HipKernelError(f"{name}: the workspace must be contiguous")
+    return workspace
+
+
+def warp_error_workspace_elems(T, H, W):
+    """fp64 elements of workspace ``warp_error`` needs (insv2v_warp_error_workspace_bytes / 8); <= 0: the entry refuses the size."""
+    n = _lib.load().insv2v_warp_error_workspace_bytes(T, H, W)
+    return n // 8 if n > 0 else n
+
+
+def frame_fidelity_workspace_elems(T, H, W):
+    n = _lib.load().insv2v_frame_fidelity_workspace_bytes(T, H, W)
+    return n // 8 if n > 0 else n
+
+
+def frame_fidelity_tile():
+    """(rows, columns) of SSIM centres one workgroup of insv2v_frame_fidelity owns."""
+    r, c = C.c_int32(), C.c_int32()
+    _lib.load().insv2v_frame_fidelity_tile(_byref(r), _byref(c))
+    return r.value, c.value
+
+
+def warp_error(frames, fwd, bwd=None, region=None, *, scale=1.0, shift=0.0, alpha=0.01, beta=0.5, return_maps=False, out=None, workspace=None):
+    """insv2v_warp_error: ``frames`` [T,3,H,W] fp16 / fp32 (any view with contiguous rows; ``clamp(x * scale + shift, 0, 1)`` as it is
+    read), ``fwd`` / ``bwd`` [T-1,2,H,W] fp32 (``bwd`` None: no consistency check), ``region`` [T,H,W] fp32 or None -> fp64 sums
+    [T-1,3] = (sum valid w err, sum valid w, valid count), and with ``return_maps`` also (err_map, valid_map) [T-1,H,W] fp32.
+    ``out``: the preallocated (sums, err_map or None, valid_map or None)."""
+    lib = _lib.load()
+    d = _lib.WarpErrorDesc()
+    T, _, H, W = _frames_view(d.a, frames, "warp_error.frames", scale, shift)
+    P = max(T - 1, 0)
+    _plain(fwd, (P, 2, H, W), "warp_error.fwd")
+    if bwd is not None:
+        _plain(bwd, (P, 2, H, W), "warp_error.bwd")
+    if region is not None:
+        _plain(region, (T, H, W), "warp_error.region")
+    if out is None:
+        maps = [torch.empty((P, H, W), device=frames.device, dtype=torch.float32) for _ in range(2)] if return_maps else [None, None]
+        out = (torch.empty((P, 3), device=frames.device, dtype=torch.float64), *maps)
+    sums, err_map, valid_map = out
+    _plain(sums, (P, 3), "warp_error.out.sums", torch.float64)
+    for name, t in (("err_map", err_map), ("valid_map", valid_map)):
+        if t is not None:
+            _plain(t, (P, H, W), "warp_error.out." + name)
+    ws = _score_workspace(lib.insv2v_warp_error_workspace_bytes(T, H, W), frames.device, workspace, "warp_error")
+    d.fwd, d.bwd, d.w, d.sums, d.err_map, d.valid_map = fwd.data_ptr() or None, _ptr(bwd), _ptr(region), sums.data_ptr() or None, _ptr(err_map), _ptr(valid_map)
+    d.workspace, d.workspace_bytes = ws.data_ptr() or None, ws.numel() * 8
+    d.T, d.H, d.W, d.alpha, d.beta = T, H, W, alpha, beta
+    check(lib.insv2v_warp_error(_byref(d), _stream()), "insv2v_warp_error")
+    return (sums, err_map, valid_map) if return_maps else sums
+
+
+def frame_fidelity(x, y, region=None, *, x_affine=(1.0, 0.0), y_affine=(1.0, 0.0), out=None, workspace=None):
+    """insv2v_frame_fidelity: source ``x`` and edit ``y`` [T,3,H,W] (each fp16 or fp32, with its own strides and (scale, shift)),
+    ``region`` [T,H,W] fp32 or None -> fp64 sums [T, 10] in the order of ``FIDELITY_KEYS``."""
+    lib = _lib.load()
+    d = _lib.FidelityDesc()
+    shape = _frames_view(d.x, x, "frame_fidelity.x", *x_affine)
+    if _frames_view(d.y, y, "frame_fidelity.y", *y_affine) != shape:
+        raise _lib.HipKernelError(f"frame_fidelity: x {shape} and y {tuple(y.shape)} differ")
+    T, _, H, W = shape
+    if region is not None:
+        _plain(region, (T, H, W), "frame_fidelity.region")
+    if out is None:
+        out = torch.empty((T, _lib.FIDELITY_K), device=x.device, dtype=torch.float64)
+    _plain(out, (T, _lib.FIDELITY_K), "frame_fidelity.out", torch.float64)
+    ws = _score_workspace(lib.insv2v_frame_fidelity_workspace_bytes(T, H, W), x.device, workspace, "frame_fidelity")
+    d.w, d.sums, d.workspace, d.workspace_bytes = _ptr(region), out.data_ptr() or None, ws.data_ptr() or None, ws.numel() * 8
+    d.T, d.H, d.W = T, H, W
+    check(lib.insv2v_frame_fidelity(_byref(d), _stream()), "insv2v_frame_fidelity")
+    return out

@@ -11,6 +11,8 @@ the HIP kernels with the BPE vocabulary from ``--tokenizer-dir``), writing the r
 
 With ``--score-ckpt FILE --score-out FILE.json`` (or ``--score-synthetic`` next to ``--synthetic``) every unit is scored after its edit
 with CLIP on the HIP kernels (``insv2v/clip_score.py``: the reference's ``ClipSimilarity`` numbers, text alignment, frame consistency).
+``--score-pixels`` / ``--score-warp`` add the pixel-space scores to the same records, with or without a CLIP scorer
+(``insv2v/pixel_score.py``: per-frame MSE / PSNR / SSIM against the source, inside and outside the unit's mask, and the flow warp error).
 
 Masks: drawn per frame or still (``mask=``, the "mask" entry of a ``--units`` file, ``--mask-file``), estimated from the prompt
 (``mask="auto"``, ``--auto-mask``), or drawn on one frame and tracked through the video with optical flow (``mask_key=``, ``--mask-key``:
@@ -477,6 +479,12 @@ def build_parser():
     p.add_argument("--score-name", type=str, default="ViT-L/14", help="the CLIP model --score-ckpt holds (the reference's ViT names)")
     p.add_argument("--score-out", type=str, default=None, help="JSON file for the scores: one record per unit")
     p.add_argument("--score-synthetic", action="store_true", help="with --synthetic: score with a key-hashed CLIP (no checkpoint needed)")
+    p.add_argument("--score-pixels", action="store_true",
+                   help="add per-frame mse / psnr / ssim of every edit against its source to the --score-out records, and with a mask (drawn, "
+                        "tracked or estimated) the same inside and outside it (insv2v/pixel_score.py); needs no CLIP scorer")
+    p.add_argument("--score-warp", action="store_true",
+                   help="add the flow warp error of every edit (and of its source) along the source video's optical flow to the --score-out "
+                        "records; the flows come from the estimator of --raft-ckpt (--synthetic: key-hashed weights)")
     p.add_argument("--synthetic-tiny", action="store_true", help="with --synthetic: the reduced-width UNet / VAE (and scorer) configurations")
     return p
 
@@ -528,7 +536,12 @@ def check_args(args):
         raise SystemExit("--score-synthetic needs --synthetic N (real units are scored with --score-ckpt FILE)")
     if score_synth and score_ckpt:
         raise SystemExit("--score-synthetic and --score-ckpt are two scorers: pass one")
-    if score_out and not (score_ckpt or score_synth):
+    score_pixels, score_warp = getattr(args, "score_pixels", False), getattr(args, "score_warp", False)
+    if score_warp and not (args.raft_ckpt or args.synthetic):
+        raise SystemExit("--score-warp needs --raft-ckpt FILE (torchvision raft_large weights): the flows the frames are warped along come from that estimator")
+    if (score_pixels or score_warp) and not score_out:
+        raise SystemExit("--score-pixels / --score-warp need --score-out FILE.json for the scores")
+    if score_out and not (score_ckpt or score_synth or score_pixels or score_warp):
         raise SystemExit("--score-out needs a scorer: --score-ckpt FILE (or --score-synthetic with --synthetic N)")
     if (score_ckpt or score_synth) and not score_out:
         raise SystemExit("--score-ckpt / --score-synthetic need --score-out FILE.json for the scores")
@@ -551,6 +564,26 @@ def score_record(scorer, unit, frames, edited, source_text, edit_text):
     """One record of --score-out: the unit id, the five per-frame lists and the two means (clip_score.ClipSimilarity.score_edit)."""
     r = scorer.score_edit(frames, edited, source_text, edit_text)
     return {"unit": int(unit), **{k: (v.tolist() if torch.is_tensor(v) else v) for k, v in r.items()}}
+
+
+PIXEL_FIDELITY_KEYS = ("mse", "psnr", "ssim")   # and, for a unit with a mask, each with _inside and _outside
+PIXEL_WARP_KEYS = ("warp_error", "warp_error_source", "warp_error_mean", "warp_error_source_mean", "valid_fraction")
+
+
+def pixel_record(args, frames, edited, mask=None, flow_estimator=None):
+    """What --score-pixels / --score-warp add to a unit's record (pixel_score.score_pixels): the fidelity fields (per-frame lists; with a
+    mask also _inside / _outside) and / or the warp fields (per-pair lists and the two means).  ``inf`` (a region the edit left
+    bit-identical) and ``nan`` (an empty region) are written as json's Infinity / NaN."""
+    from .pixel_score import score_pixels
+    pixels, warp = getattr(args, "score_pixels", False), getattr(args, "score_warp", False)
+    if not (pixels or warp):
+        return {}
+    r = score_pixels(frames, edited, flow_estimator=flow_estimator if warp else None, mask=mask if pixels else None)
+    return {k: v.tolist() for k, v in r.items() if (pixels if k not in PIXEL_WARP_KEYS else warp)}
+
+
+def want_pixel_scores(args):
+    return bool(getattr(args, "score_pixels", False) or getattr(args, "score_warp", False))
 
 
 def write_scores(path, records, rank=0, world=1):
@@ -596,9 +629,9 @@ def load_mask_file(args):
 
 
 def build_flow_estimator(args, device):
-    """The CLI's flow estimator of --mask-key (None without it): RAFT on the HIP kernels with the weights of --raft-ckpt, key-hashed
-    weights in a --synthetic run."""
-    if getattr(args, "mask_key", None) is None:
+    """The CLI's flow estimator of --mask-key and --score-warp (None without either): RAFT on the HIP kernels with the weights of
+    --raft-ckpt, key-hashed weights in a --synthetic run."""
+    if getattr(args, "mask_key", None) is None and not getattr(args, "score_warp", False):
         return None
     from .raft import RAFTFlow
     if args.raft_ckpt:
@@ -660,8 +693,9 @@ def run_dataset(args, model, pipe, rank=0, world=1, scorer=None):
     records = []
     auto = auto_mask_unit(args)
     track, drawn = mask_track_unit(args), load_mask_file(args)   # drawn masks are named by video here
-    more = {"flow_estimator": build_flow_estimator(args, model.unet.device)} if track else {}
-    want_masks = {"return_mask": True} if (auto or track) and getattr(args, "mask_out", None) else {}   # (a plain run carries no new keyword)
+    estimator = build_flow_estimator(args, model.unet.device)
+    more = {"flow_estimator": estimator} if track else {}
+    want_masks = {"return_mask": True} if (auto or track) and (getattr(args, "mask_out", None) or getattr(args, "score_pixels", False)) else {}   # (a plain run carries no new keyword)
     masks = {}
     for ci, (video_id, text_cfg, video_cfg, num_frames, image_size) in enumerate(combos):
         if ci % world != rank:
@@ -693,13 +727,18 @@ def run_dataset(args, model, pipe, rank=0, world=1, scorer=None):
         for (gif_path, image_dir, u, prompt), edited in zip(todo, edits):
             if want_masks:
                 edited, masks[u["unit"]] = edited
+            rec = {"unit": int(u["unit"])}
             if scorer is not None:   # the edited frames are still on the device
-                records.append(score_record(scorer, u["unit"], frames, edited, batch["original"], prompt))
+                rec.update(score_record(scorer, u["unit"], frames, edited, batch["original"], prompt))
+            if want_pixel_scores(args):   # the region: the unit's image-resolution mask - tracked or estimated if the run made one, else as drawn
+                est = masks.get(u["unit"])
+                rec.update(pixel_record(args, frames, edited, est["mask"] if est is not None else u.get("mask"), estimator))
+            records.append(rec)
             save_tensor_to_gif(torch.cat([frames.float().cpu(), edited.float().cpu()], dim=4), gif_path, fps=5)
             save_tensor_to_images(edited.float().cpu(), image_dir)
-    if scorer is not None:
+    if scorer is not None or want_pixel_scores(args):
         write_scores(args.score_out, records, rank, world)
-    if want_masks:
+    if want_masks and getattr(args, "mask_out", None):
         write_masks(args.mask_out, masks, rank, world)
 
 
@@ -773,8 +812,9 @@ def main(argv=None):
         raise SystemExit("--mask-file next to the \"mask\" entry of the --units file are two masks: pass one")
     if track and not drawn and data.get("mask") is None:
         raise SystemExit("--mask-key needs a mask to track: --mask-file FILE.pt, the \"mask\" entry of a --units file, or --synthetic-mask")
-    more = {"flow_estimator": build_flow_estimator(args, f"cuda:{local}")} if track else {}
-    want_masks = {"return_mask": True} if (auto or track) and args.mask_out else {}
+    estimator = build_flow_estimator(args, f"cuda:{local}")
+    more = {"flow_estimator": estimator} if track else {}
+    want_masks = {"return_mask": True} if (auto or track) and (args.mask_out or args.score_pixels) else {}
     est_masks = {}
     masks = data.get("mask")   # optional [n,T,H,W] / [n,1,H,W]
 
@@ -806,13 +846,19 @@ def main(argv=None):
             for i, (_, est) in zip(mine, local_out):
                 est_masks[ci * n + i] = est
             local_out = [img for img, _ in local_out]
-        for i, edited in zip(mine, local_out if scorer is not None else []):
-            records.append(score_record(scorer, ci * n + i, data["frames"][i:i + 1], edited, *_score_texts(data, i, scorer)))
+        for i, edited in zip(mine, local_out if scorer is not None or want_pixel_scores(args) else []):
+            rec = {"unit": ci * n + i}
+            if scorer is not None:
+                rec.update(score_record(scorer, ci * n + i, data["frames"][i:i + 1], edited, *_score_texts(data, i, scorer)))
+            if want_pixel_scores(args):   # the region: the unit's image-resolution mask - tracked or estimated if the run made one, else as drawn
+                est = est_masks.get(ci * n + i)
+                rec.update(pixel_record(args, data["frames"][i:i + 1], edited, est["mask"] if est is not None else edit(i)["mask"], estimator))
+            records.append(rec)
         local_out = torch.cat(local_out, 0).half() if local_out else torch.zeros((0, *item_shape), device=model.unet.device).half()
         outs.append(gather_frames(local_out, n, item_shape=item_shape))
-    if scorer is not None:
+    if scorer is not None or want_pixel_scores(args):
         write_scores(args.score_out, records, rank, world)
-    if want_masks:
+    if want_masks and args.mask_out:
         write_masks(args.mask_out, est_masks, rank, world)
     if rank == 0:
         os.makedirs(os.path.dirname(args.out) or ".", exist_ok=True)
