@@ -1008,6 +1008,40 @@ int insv2v_frame_fidelity(const insv2v_fidelity_desc* d, insv2v_stream_t stream)
 /* The kernel's tile of SSIM centres (rows, columns): what the tests name their shapes from.  Returns 0. */
 int insv2v_frame_fidelity_tile(int32_t* rows, int32_t* cols);
 
+/*
+ * ---- stabilizing an edit along the source video's flow (an addition to ABI 15: no existing struct or entry changes) ---------------------
+ * A temporal filter on decoded frames (csrc/temporal_filter.hip; tests/temporal_filter_ref.py restates the
+ * definition in float64).  E [T,3,H,W] is the edit, read as it is; A is the guide (the SOURCE video), read as a = clamp(x * scale +
+ * shift, 0, 1) like every insv2v_frames_view.  Neighbour k of frame t is frame t + offsets[k]; G_{t,k} = flow[k][t] is defined on frame t
+ * and points into that frame (the convention of insv2v_warp_image), U_{t,k} = valid[k][t] is 1 where the trajectory may be followed.
+ * A neighbour outside the video, or with U <= 1/2, is SKIPPED (its G, E and A are not read: a NaN there cannot leak).  For the others,
+ * in the order k = 0 .. K-1, with p = x + G(x), its clamp and the sample S(.) exactly as defined for insv2v_mask_track_step:
+ *   d2  = (1/3) sum_c (a_t[c](x) - S(a_{t+k}[c]))^2          fp32: the three squares added in channel order, then divided by 3
+ *   w_k = strength * expf(d2 * (-1 / (2 sigma^2)))             the factor is formed in double on the host and rounded once
+ *   out_t[c](x) = E_t[c](x) + (sum_k w_k (S(E_{t+k}[c]) - E_t[c](x))) / (1 + sum_k w_k)
+ * and out = E_t[c](x), its own bits, when that quotient is 0: a pixel without a valid neighbour and a video that is constant along its
+ * trajectories come back bit for bit.  All arithmetic is fp32; the output has E's dtype and is rounded once, on the store.  Every thread
+ * writes its own pixel: no atomics, two calls give the same bits.  Nothing is allocated.
+ * INSV2V_EINVAL, nothing launched and no output touched: a NULL descriptor or pointer; T < 1; K outside 1 .. INSV2V_TFILTER_MAX_K; an
+ * offset that is 0 or beyond +-INSV2V_TFILTER_MAX_RADIUS; H <= 1 or W <= 1; sigma not finite or <= 0; strength outside (0, 1]; a guide
+ * affine that is not finite; a negative stride or a row stride below W; T above 65535 or a plane beyond the grid; an output that
+ * overlaps E, A, flow or valid (a pixel reads other frames that other threads write).
+ */
+#define INSV2V_TFILTER_MAX_K 8
+#define INSV2V_TFILTER_MAX_RADIUS 4
+typedef struct insv2v_temporal_filter_desc {
+    insv2v_frames_view e;    /* the edit; scale / shift are not read */
+    insv2v_frames_view a;    /* the guide */
+    const float* flow;       /* [K,T,2,H,W] contiguous */
+    const float* valid;      /* [K,T,H,W] contiguous, 0 or 1 */
+    void* out;               /* [T,3,H,W] of E's dtype, element strides below, x contiguous */
+    int64_t out_stride_t, out_stride_c, out_stride_h;
+    int32_t offsets[INSV2V_TFILTER_MAX_K];
+    int32_t K, T, H, W;
+    float sigma, strength;
+} insv2v_temporal_filter_desc;
+int insv2v_temporal_filter(const insv2v_temporal_filter_desc* d, insv2v_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -169,6 +169,16 @@ class FidelityDesc(C.Structure):
                 ("T", c_i32), ("H", c_i32), ("W", c_i32)]
 
 
+TFILTER_MAX_K, TFILTER_MAX_RADIUS = 8, 4   # INSV2V_TFILTER_MAX_K, INSV2V_TFILTER_MAX_RADIUS
+
+
+class TemporalFilterDesc(C.Structure):
+    """insv2v_temporal_filter_desc (csrc/temporal_filter.hip)."""
+    _fields_ = [("e", FramesView), ("a", FramesView), ("flow", c_p), ("valid", c_p), ("out", c_p),
+                ("out_stride_t", c_i64), ("out_stride_c", c_i64), ("out_stride_h", c_i64), ("offsets", c_i32 * TFILTER_MAX_K),
+                ("K", c_i32), ("T", c_i32), ("H", c_i32), ("W", c_i32), ("sigma", c_f32), ("strength", c_f32)]
+
+
 # name -> (restype, argtypes); mirrors include/insv2v_hip.h one to one.
 SIGNATURES = {
     "insv2v_abi_version": (c_i32, []),
@@ -240,6 +250,7 @@ SIGNATURES = {
     "insv2v_frame_fidelity_workspace_bytes": (c_i64, [c_i32, c_i32, c_i32]),
     "insv2v_frame_fidelity": (c_i32, [C.POINTER(FidelityDesc), c_p]),
     "insv2v_frame_fidelity_tile": (c_i32, [C.POINTER(c_i32), C.POINTER(c_i32)]),
+    "insv2v_temporal_filter": (c_i32, [C.POINTER(TemporalFilterDesc), c_p]),
 }
 
 _lib = None

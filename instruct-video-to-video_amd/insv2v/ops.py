@@ -1301,3 +1301,35 @@ def frame_fidelity(x, y, region=None, *, x_affine=(1.0, 0.0), y_affine=(1.0, 0.0
     d.T, d.H, d.W = T, H, W
     check(lib.insv2v_frame_fidelity(_byref(d), _stream()), "insv2v_frame_fidelity")
     return out
+
+
+# ----------------------------------------------------------------------------- stabilizing an edit (insv2v/temporal_filter.py)
+def temporal_filter(edited, guide, flow, valid, offsets, *, sigma=0.1, strength=1.0, guide_affine=(1.0, 0.0), out=None):
+    """insv2v_temporal_filter (tests/temporal_filter_ref.py is the definition): ``edited`` and ``guide`` [T,3,H,W],
+    each fp16 or fp32 and any view with contiguous rows (the guide is read as ``clamp(x * scale + shift, 0, 1)``), ``flow`` [K,T,2,H,W] and
+    ``valid`` [K,T,H,W] fp32 contiguous, ``offsets`` the K neighbour offsets -> the filtered frames [T,3,H,W] in ``edited``'s dtype.
+    ``out``: preallocated, any view with contiguous rows; the entry refuses one that overlaps an input."""
+    lib = _lib.load()
+    d = _lib.TemporalFilterDesc()
+    shape = _frames_view(d.e, edited, "temporal_filter.edited", 1.0, 0.0)
+    if _frames_view(d.a, guide, "temporal_filter.guide", *guide_affine) != shape:
+        raise _lib.HipKernelError(f"temporal_filter: edited {shape} and guide {tuple(guide.shape)} differ")
+    T, _, H, W = shape
+    offsets = [int(k) for k in offsets]
+    K = len(offsets)
+    if K > _lib.TFILTER_MAX_K:
+        raise _lib.HipKernelError(f"temporal_filter: {K} neighbours, at most {_lib.TFILTER_MAX_K}")
+    _plain(flow, (K, T, 2, H, W), "temporal_filter.flow")
+    _plain(valid, (K, T, H, W), "temporal_filter.valid")
+    if out is None:
+        out = torch.empty(shape, device=edited.device, dtype=edited.dtype)
+    ov = _lib.FramesView()
+    if _frames_view(ov, out, "temporal_filter.out", 1.0, 0.0) != shape or out.dtype != edited.dtype:
+        raise _lib.HipKernelError(f"temporal_filter: out {tuple(out.shape)} {out.dtype} must be {shape} {edited.dtype}")
+    d.flow, d.valid, d.out = flow.data_ptr() or None, valid.data_ptr() or None, ov.p
+    d.out_stride_t, d.out_stride_c, d.out_stride_h = ov.stride_t, ov.stride_c, ov.stride_h
+    for i, k in enumerate(offsets):
+        d.offsets[i] = k
+    d.K, d.T, d.H, d.W, d.sigma, d.strength = K, T, H, W, sigma, strength
+    check(lib.insv2v_temporal_filter(_byref(d), _stream()), "insv2v_temporal_filter")
+    return out

@@ -17,6 +17,9 @@ with CLIP on the HIP kernels (``insv2v/clip_score.py``: the reference's ``ClipSi
 Masks: drawn per frame or still (``mask=``, the "mask" entry of a ``--units`` file, ``--mask-file``), estimated from the prompt
 (``mask="auto"``, ``--auto-mask``), or drawn on one frame and tracked through the video with optical flow (``mask_key=``, ``--mask-key``:
 ``insv2v/mask_track.py``).
+
+``stabilize=`` / ``--stabilize`` filters a unit's decoded frames along the SOURCE video's optical flow, once per unit and after its last
+window (``insv2v/temporal_filter.py``): the switch to pull when ``--score-warp`` shows flicker.
 """
 import argparse
 import os
@@ -60,14 +63,21 @@ AUTO_MASK_KEYS = ("n_maps", "mask_strength", "clamp_ratio", "threshold", "smooth
 MASK_TRACK_KEYS = ("occlusion", "alpha", "beta", "fill")
 
 
-def check_edit_args(frames_shape, mask=None, strength=1.0, mask_mode="max", auto_mask=None, mask_key=None, mask_flows=None, mask_track=None):
+STABILIZE_KEYS = ("radius", "sigma", "strength", "occlusion", "alpha", "beta")
+
+
+def check_edit_args(frames_shape, mask=None, strength=1.0, mask_mode="max", auto_mask=None, mask_key=None, mask_flows=None, mask_track=None,
+                    stabilize=None, stabilize_flows=None):
     """Host-side check of the localized / partial edit controls (nothing is launched): ``strength`` in (0, 1], ``mask_mode`` "mean" or
     "max", ``mask`` a floating-point [1,T,H,W] or [1,1,H,W] tensor for frames [1,T,3,H,W] with H and W multiples of 8 - or the string
     "auto" (the mask is estimated from the prompt, ``InferenceIP2PVideo.estimate_mask``), then optionally with ``auto_mask``, a dict of
     that method's keywords (``AUTO_MASK_KEYS``).  ``mask_key`` (a frame index: the mask, then a [1,1,H,W] tensor, is drawn on that frame
     and tracked through the video, ``insv2v/mask_track.py``) optionally with ``mask_flows``, a dict(fwd=, bwd=) of [T-1,2,H,W] flows, and
-    ``mask_track``, a dict of ``propagate_mask``'s keywords (``MASK_TRACK_KEYS``)."""
+    ``mask_track``, a dict of ``propagate_mask``'s keywords (``MASK_TRACK_KEYS``).  ``stabilize`` (None, True or a dict of
+    ``temporal_filter.stabilize``'s parameters, ``STABILIZE_KEYS``) optionally with ``stabilize_flows``, a dict(fwd=, bwd=) of the source
+    video's [T-1,2,H,W] flows."""
     strength_to_start(strength, 1)
+    _check_stabilize_args(frames_shape, stabilize, stabilize_flows)
     if mask_key is None and (mask_flows is not None or mask_track is not None):
         raise ValueError("mask_flows / mask_track belong to a tracked mask: pass mask_key=, the frame the mask is drawn on, with them")
     if mask_key is not None:
@@ -125,6 +135,39 @@ def _check_track_args(frames_shape, mask, mask_key, mask_flows, mask_track):
                 raise ValueError(f"mask_flows[{k!r}] {tuple(getattr(f, 'shape', ()))} must be [{T - 1},2,{H},{W}] for frames {tuple(frames_shape)}")
         if track.get("occlusion", True) and T > 1 and (mask_flows.get("fwd") is None or mask_flows.get("bwd") is None):
             raise ValueError("mask_flows: the occlusion check of a tracked mask needs both fwd and bwd (or mask_track=dict(occlusion=False))")
+
+
+def _stabilize_params(stabilize):
+    """None when the filter is off, else the dict of its parameters (``True``: the defaults)."""
+    if stabilize is None or stabilize is False:
+        return None
+    return {} if stabilize is True else stabilize
+
+
+def _check_stabilize_args(frames_shape, stabilize, stabilize_flows):
+    """The ``stabilize`` part of ``check_edit_args``."""
+    from .temporal_filter import check_filter_args
+    params = _stabilize_params(stabilize)
+    if params is None:
+        if stabilize_flows is not None:
+            raise ValueError("stabilize_flows belongs to a stabilized edit: pass stabilize=True (or a dict of its parameters) with it")
+        return
+    if not isinstance(params, dict) or set(params) - set(STABILIZE_KEYS):
+        raise ValueError(f"stabilize must be None, True or a dict with keys among {STABILIZE_KEYS}, got {stabilize!r}")
+    try:
+        check_filter_args(**params)
+    except ValueError as e:
+        raise ValueError(f"stabilize (the parameters of the temporal filter): {e}") from None
+    b, T, _, H, W = frames_shape
+    if b != 1:
+        raise ValueError(f"stabilize needs frames [1,T,3,H,W], not {tuple(frames_shape)}")
+    if stabilize_flows is not None:
+        if not isinstance(stabilize_flows, dict) or set(stabilize_flows) - {"fwd", "bwd"} or stabilize_flows.get("fwd") is None \
+                or (params.get("occlusion", True) and stabilize_flows.get("bwd") is None):
+            raise ValueError(f"stabilize_flows must be a dict(fwd=, bwd=) of the source video's [{T - 1},2,{H},{W}] flows (bwd may be missing with occlusion=False)")
+        for k, f in stabilize_flows.items():
+            if f is not None and (not torch.is_tensor(f) or not f.is_floating_point() or tuple(f.shape) != (T - 1, 2, H, W)):
+                raise ValueError(f"stabilize_flows[{k!r}] {tuple(getattr(f, 'shape', ()))} must be a floating-point [{T - 1},2,{H},{W}] for frames {tuple(frames_shape)}")
 
 
 def _start_time(inf_pipe, strength):
@@ -206,6 +249,31 @@ def _track_mask(inf_pipe, frames, mask, mask_key, mask_flows, flow_estimator, ma
     return propagate_mask(mask.to(device=dev), mask_key, flows["fwd"], flows["bwd"], **track)
 
 
+def _stabilize_flows(inf_pipe, frames, params, stabilize_flows, mask_flows, flow_estimator):
+    """``stabilize=``: the source video's flows the filter follows -> (dict(fwd, bwd) or None for a single frame, whether they were
+    computed here).  In this order: ``stabilize_flows``, the ``mask_flows`` of a tracked mask when they hold both sets, ``flow_estimator``,
+    the pipe's own estimator - then ONE ``pair_flows(both=True)`` of the whole unit, which also serves its tracked mask."""
+    from .mask_track import pair_flows
+    if frames.shape[1] == 1:   # nothing to filter: no flow is needed, none is computed
+        return None, False
+    if stabilize_flows is not None:
+        return stabilize_flows, False
+    if mask_flows is not None and mask_flows.get("fwd") is not None and mask_flows.get("bwd") is not None:
+        return mask_flows, False
+    est = flow_estimator if flow_estimator is not None else getattr(inf_pipe, "flow_estimator", None)
+    if est is None:
+        raise RuntimeError("stabilized edit (stabilize=) without a flow source: pass stabilize_flows=, mask_flows= or flow_estimator=, or build the pipe with flow_estimator=")
+    return pair_flows(frames, est, both=True), True
+
+
+def _stabilize(frames, image, params, flows, mask_img):
+    """The unit's finished frames [1,T,3,H,W], filtered once over the whole unit - also across the hand-over of its windows."""
+    from .temporal_filter import stabilize
+    if flows is None:
+        return image
+    return stabilize(frames, image, flows=flows, mask=None if mask_img is None else mask_img[None], **params)
+
+
 def _result(image, latent, est, return_latent, return_mask):
     out = (image,) + ((latent,) if return_latent else ()) + ((est,) if return_mask else ())
     return out if len(out) > 1 else image
@@ -215,7 +283,7 @@ def _result(image, latent, est, return_latent, return_mask):
 def edit_video(model, inf_pipe, frames, text_cond, text_uncond, text_cfg=7.5, video_cfg=1.8, frames_in_batch=16,
                num_ref_frames=4, init_noises=None, enc_noise=None, flows_per_window=None, return_latent=False, cond=None,
                seed=None, unit=0, mask=None, strength=1.0, mask_mode="max", auto_mask=None, return_mask=False,
-               mask_key=None, mask_flows=None, flow_estimator=None, mask_track=None):
+               mask_key=None, mask_flows=None, flow_estimator=None, mask_track=None, stabilize=None, stabilize_flows=None):
     """frames [1,T,3,H,W] in [-1,1] -> edited frames [1,T,3,H,W] clipped to [-1,1].
 
     ``seed`` (default None: every draw comes from the global torch generators, as before) makes the edit reproducible: the posterior
@@ -250,10 +318,22 @@ def edit_video(model, inf_pipe, frames, text_cond, text_uncond, text_cfg=7.5, vi
     ``mask_track.pair_flows`` - are chained into the flow from every frame to frame k and the mask is sampled once per frame
     (``mask_track.propagate_mask``; ``mask_track``: a dict of its keywords, ``MASK_TRACK_KEYS``).  Computed once per unit from the whole
     video, before the first window; from there it is a user's [1,T,H,W] mask.  ``return_mask=True`` then returns ``propagate_mask``'s
-    dict (``mask``, ``valid``, ``flow_to_key``).  Without ``mask_key`` nothing of this runs."""
-    check_edit_args(frames.shape, mask, strength, mask_mode, auto_mask, mask_key, mask_flows, mask_track)
+    dict (``mask``, ``valid``, ``flow_to_key``).  Without ``mask_key`` nothing of this runs.
+
+    ``stabilize`` (True, or a dict of ``temporal_filter.stabilize``'s parameters, ``STABILIZE_KEYS``): the decoded frames of the WHOLE unit
+    are filtered along the source video's optical flow after its last window, which also smooths the jump where one
+    window hands over to the next; the result returned (and scored) is the filtered one, composited against the input under a mask like
+    the edit itself.  The flows are ``stabilize_flows`` (dict(fwd=, bwd=) of [T-1,2,H,W]), else the ``mask_flows`` of a tracked mask, else
+    computed by ``flow_estimator`` (default: the pipe's own) - once per unit: a tracked mask and the filter share one
+    ``pair_flows(both=True)``.  Without ``stabilize`` nothing of this runs."""
+    check_edit_args(frames.shape, mask, strength, mask_mode, auto_mask, mask_key, mask_flows, mask_track, stabilize, stabilize_flows)
     dev = model.unet.device
     est = None
+    stab, sflows = _stabilize_params(stabilize), None
+    if stab is not None:   # before the first window: a missing flow source raises before anything is sampled
+        sflows, computed = _stabilize_flows(inf_pipe, frames, stab, stabilize_flows, mask_flows, flow_estimator)
+        if computed and mask_key is not None and mask_flows is None:
+            mask_flows = sflows
     if mask_key is not None:
         est = _track_mask(inf_pipe, frames, mask, mask_key, mask_flows, flow_estimator, mask_track, dev)
         mask = est["mask"]
@@ -301,6 +381,8 @@ def edit_video(model, inf_pipe, frames, text_cond, text_uncond, text_cfg=7.5, vi
         preds.append(pred[:, R:])
     latent = torch.cat(preds, dim=1)
     image = plan.finish(model.decode_latent_to_image(latent), frames)
+    if stab is not None:
+        image = _stabilize(frames, image, stab, sflows, plan.mask_img)
     return _result(image, latent, est, return_latent, return_mask)
 
 
@@ -325,19 +407,21 @@ def edit_videos(model, inf_pipe, units, frames_in_batch=16, num_ref_frames=4, re
     own, before the stacked windows start - so it is bit for bit the mask ``edit_video`` estimates for that unit.  ``return_mask``: as
     for ``edit_video``, per unit.  A unit may carry ``mask_key`` (and ``mask_flows``, ``mask_track``) as for ``edit_video``: its mask is
     tracked alone, before the stacked windows start, bit for bit as ``edit_video`` tracks it; ``flow_estimator`` is the flow source of
-    the units without ``mask_flows`` (default: the pipe's own).  Tracked, drawn, auto and unmasked units stack together."""
+    the units without ``mask_flows`` (default: the pipe's own).  Tracked, drawn, auto and unmasked units stack together.  A unit may carry
+    ``stabilize`` (and ``stabilize_flows``) as for ``edit_video``: it is filtered alone, after the stacked windows have finished, bit for
+    bit as ``edit_video`` filters it; stabilized and plain units stack together."""
     if len(units) == 0:
         return []
     for u in units:
         check_edit_args(u["frames"].shape, u.get("mask"), u.get("strength", 1.0), u.get("mask_mode", "max"), u.get("auto_mask"),
-                        u.get("mask_key"), u.get("mask_flows"), u.get("mask_track"))
+                        u.get("mask_key"), u.get("mask_flows"), u.get("mask_track"), u.get("stabilize"), u.get("stabilize_flows"))
     if len({_start_time(inf_pipe, u.get("strength", 1.0)) for u in units}) > 1:
         raise ValueError("edit_videos: the units of one call must share the number of executed steps (strength); edit the others separately")
     wants_flow = hasattr(inf_pipe, "obtain_flow_batched")
     ids = [u.get("unit", j) for j, u in enumerate(units)]
     if len(units) == 1:
         keys = ("text_cfg", "video_cfg", "init_noises", "enc_noise", "cond", "flows_per_window", "mask", "strength", "mask_mode", "auto_mask",
-                "mask_key", "mask_flows", "mask_track")
+                "mask_key", "mask_flows", "mask_track", "stabilize", "stabilize_flows")
         more = {"return_mask": True} if return_mask else {}   # (a plain call carries no new keyword)
         if flow_estimator is not None:
             more["flow_estimator"] = flow_estimator
@@ -357,8 +441,13 @@ def edit_videos(model, inf_pipe, units, frames_in_batch=16, num_ref_frames=4, re
             cond = z / model.scale_factor
         conds, refs = split_batch(cond, frames_in_batch, num_ref_frames)
         mask, est = u.get("mask"), None
+        stab, sflows, mask_flows = _stabilize_params(u.get("stabilize")), None, u.get("mask_flows")
+        if stab is not None:
+            sflows, computed = _stabilize_flows(inf_pipe, u["frames"], stab, u.get("stabilize_flows"), mask_flows, flow_estimator)
+            if computed and u.get("mask_key") is not None and mask_flows is None:
+                mask_flows = sflows
         if u.get("mask_key") is not None:   # tracked here, alone, before the first stacked window of any unit
-            est = _track_mask(inf_pipe, u["frames"], mask, u["mask_key"], u.get("mask_flows"), flow_estimator, u.get("mask_track"), dev)
+            est = _track_mask(inf_pipe, u["frames"], mask, u["mask_key"], mask_flows, flow_estimator, u.get("mask_track"), dev)
             mask = est["mask"]
         if isinstance(mask, str):   # "auto": estimated here, alone, before the first stacked window of any unit
             est = _estimate_mask(model, inf_pipe, z, cond, u["text_cond"], u["text_uncond"], frames_in_batch, u.get("auto_mask"), seed, uid)
@@ -367,7 +456,7 @@ def edit_videos(model, inf_pipe, units, frames_in_batch=16, num_ref_frames=4, re
                          frames_in_batch, num_ref_frames, z=z)
         if wants_flow and u.get("flows_per_window") is None and getattr(inf_pipe, "flow_estimator", None) is None and len(conds) > 1:
             raise RuntimeError("optical-flow pipeline without a flow source: pass flows_per_window= or build the pipe with flow_estimator=")
-        st.append(dict(u=u, unit=uid, conds=conds, refs=refs, preds=[], init=None, pred=None, plan=plan, est=est,
+        st.append(dict(u=u, unit=uid, conds=conds, refs=refs, preds=[], init=None, pred=None, plan=plan, est=est, stab=stab, sflows=sflows,
                        frame_chunks=split_batch(u["frames"], frames_in_batch, num_ref_frames)[0] if wants_flow else None))
 
     def draw(s, k, like):
@@ -413,6 +502,8 @@ def edit_videos(model, inf_pipe, units, frames_in_batch=16, num_ref_frames=4, re
     for s in st:
         latent = torch.cat(s["preds"], dim=1)
         image = s["plan"].finish(model.decode_latent_to_image(latent), s["u"]["frames"])
+        if s["stab"] is not None:   # each unit alone, after the stacked windows
+            image = _stabilize(s["u"]["frames"], image, s["stab"], s["sflows"], s["plan"].mask_img)
         outs.append(_result(image, latent, s["est"], return_latent, return_mask))
     return outs
 
@@ -485,6 +576,15 @@ def build_parser():
     p.add_argument("--score-warp", action="store_true",
                    help="add the flow warp error of every edit (and of its source) along the source video's optical flow to the --score-out "
                         "records; the flows come from the estimator of --raft-ckpt (--synthetic: key-hashed weights)")
+    p.add_argument("--stabilize", action="store_true",
+                   help="filter every edit along the SOURCE video's optical flow after its last window (insv2v/temporal_filter.py): less "
+                        "flicker and a smoother hand-over between windows; the flows come from the estimator of --raft-ckpt (--synthetic: "
+                        "key-hashed weights); the --stabilize-* values are starting points, not tuned on real footage")
+    p.add_argument("--stabilize-radius", type=int, default=None, help="frames on either side the filter averages over, 1 .. 4 (default 2)")
+    p.add_argument("--stabilize-sigma", type=float, default=None,
+                   help="how much the source may differ between the two ends of a trajectory, on [0, 1] data (default 0.1)")
+    p.add_argument("--stabilize-strength", type=float, default=None, help="in (0, 1]: the weight of a perfectly matching neighbour (default 1)")
+    p.add_argument("--stabilize-no-occlusion", action="store_true", help="with --stabilize: no forward-backward consistency check on the trajectories")
     p.add_argument("--synthetic-tiny", action="store_true", help="with --synthetic: the reduced-width UNet / VAE (and scorer) configurations")
     return p
 
@@ -529,6 +629,16 @@ def check_args(args):
             raise SystemExit("--mask-key needs --raft-ckpt FILE (torchvision raft_large weights): the flows the mask follows come from that estimator")
     elif getattr(args, "mask_no_occlusion", False):
         raise SystemExit("--mask-no-occlusion is a parameter of --mask-key")
+    if getattr(args, "stabilize", False):
+        if not (args.raft_ckpt or args.synthetic):
+            raise SystemExit("--stabilize needs --raft-ckpt FILE (torchvision raft_large weights): the flows the filter follows come from that estimator")
+        from .temporal_filter import check_filter_args
+        try:
+            check_filter_args(**stabilize_unit(args)["stabilize"])
+        except ValueError as e:
+            raise SystemExit(f"--stabilize-radius / --stabilize-sigma / --stabilize-strength: {e}")
+    elif any(getattr(args, k, None) for k in ("stabilize_radius", "stabilize_sigma", "stabilize_strength", "stabilize_no_occlusion")):
+        raise SystemExit("--stabilize-radius / --stabilize-sigma / --stabilize-strength / --stabilize-no-occlusion are parameters of --stabilize")
     if args.flows and args.units is None and not args.synthetic:
         raise SystemExit("--flows is supported with --units / --synthetic (flows are indexed by unit)")
     score_synth, score_ckpt, score_out = (getattr(args, k, None) for k in ("score_synthetic", "score_ckpt", "score_out"))
@@ -618,6 +728,16 @@ def mask_track_unit(args):
     return dict(mask_key=args.mask_key, mask_track=dict(occlusion=not getattr(args, "mask_no_occlusion", False)))
 
 
+def stabilize_unit(args):
+    """What --stabilize adds to every unit (nothing without it)."""
+    if not getattr(args, "stabilize", False):
+        return {}
+    from .temporal_filter import FILTER_DEFAULTS
+    pick = lambda k: FILTER_DEFAULTS[k] if getattr(args, "stabilize_" + k, None) is None else getattr(args, "stabilize_" + k)   # noqa: E731
+    return dict(stabilize=dict(radius=pick("radius"), sigma=pick("sigma"), strength=pick("strength"),
+                               occlusion=not getattr(args, "stabilize_no_occlusion", False)))
+
+
 def load_mask_file(args):
     """{unit id or video name: mask tensor} of --mask-file ({} without it)."""
     if not getattr(args, "mask_file", None):
@@ -629,9 +749,9 @@ def load_mask_file(args):
 
 
 def build_flow_estimator(args, device):
-    """The CLI's flow estimator of --mask-key and --score-warp (None without either): RAFT on the HIP kernels with the weights of
+    """The CLI's flow estimator of --mask-key, --stabilize and --score-warp (None without any): RAFT on the HIP kernels with the weights of
     --raft-ckpt, key-hashed weights in a --synthetic run."""
-    if getattr(args, "mask_key", None) is None and not getattr(args, "score_warp", False):
+    if getattr(args, "mask_key", None) is None and not getattr(args, "score_warp", False) and not getattr(args, "stabilize", False):
         return None
     from .raft import RAFTFlow
     if args.raft_ckpt:
@@ -694,7 +814,8 @@ def run_dataset(args, model, pipe, rank=0, world=1, scorer=None):
     auto = auto_mask_unit(args)
     track, drawn = mask_track_unit(args), load_mask_file(args)   # drawn masks are named by video here
     estimator = build_flow_estimator(args, model.unet.device)
-    more = {"flow_estimator": estimator} if track else {}
+    stab = stabilize_unit(args)
+    more = {"flow_estimator": estimator} if track or stab else {}
     want_masks = {"return_mask": True} if (auto or track) and (getattr(args, "mask_out", None) or getattr(args, "score_pixels", False)) else {}   # (a plain run carries no new keyword)
     masks = {}
     for ci, (video_id, text_cfg, video_cfg, num_frames, image_size) in enumerate(combos):
@@ -716,7 +837,7 @@ def run_dataset(args, model, pipe, rank=0, world=1, scorer=None):
                 continue
             todo.append((gif_path, image_dir, dict(frames=frames, text_cond=model.encode_text([prompt]), text_uncond=text_uncond,
                                                    text_cfg=text_cfg, video_cfg=video_cfg, cond=cond, unit=4 * ci + kinds.index(key),
-                                                   strength=getattr(args, "strength", 1.0), **auto,
+                                                   strength=getattr(args, "strength", 1.0), **auto, **stab,
                                                    **(dict(mask=drawn[batch["video_name"]], mask_mode=getattr(args, "mask_mode", "max"),
                                                            **track) if batch["video_name"] in drawn else {})), prompt))
         # the four prompts of a video share the conditioning latent and the window plan: one stacked launch chain per window (B = 12)
@@ -813,14 +934,15 @@ def main(argv=None):
     if track and not drawn and data.get("mask") is None:
         raise SystemExit("--mask-key needs a mask to track: --mask-file FILE.pt, the \"mask\" entry of a --units file, or --synthetic-mask")
     estimator = build_flow_estimator(args, f"cuda:{local}")
-    more = {"flow_estimator": estimator} if track else {}
+    stab = stabilize_unit(args)
+    more = {"flow_estimator": estimator} if track or stab else {}
     want_masks = {"return_mask": True} if (auto or track) and (args.mask_out or args.score_pixels) else {}
     est_masks = {}
     masks = data.get("mask")   # optional [n,T,H,W] / [n,1,H,W]
 
     def edit(i):
         m = masks[i:i + 1] if masks is not None else drawn.get(i)
-        return dict(dict(mask=m, strength=args.strength, mask_mode=args.mask_mode), **auto, **(track if m is not None else {}))
+        return dict(dict(mask=m, strength=args.strength, mask_mode=args.mask_mode), **auto, **stab, **(track if m is not None else {}))
     scorer = build_scorer(args, f"cuda:{local}", tok)
     records = []
     outs = []
