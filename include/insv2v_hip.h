@@ -1042,6 +1042,66 @@ typedef struct insv2v_temporal_filter_desc {
 } insv2v_temporal_filter_desc;
 int insv2v_temporal_filter(const insv2v_temporal_filter_desc* d, insv2v_stream_t stream);
 
+/*
+ * ---- growing, shrinking and feathering a mask (an addition to ABI 15: no existing struct or entry changes) --------------------------------
+ * A mask m [T,H,W] fp32 from any source becomes the two masks a localized edit wants (csrc/mask_shape.hip, DESIGN.md section 22;
+ * tests/mask_shape_ref.py restates the definition with integers and float64): `shaped`, soft, for the pixel composite, and `support`,
+ * hard and covering the whole feather, for the latent hold.  Parameters: threshold tau, grow g (pixels, negative shrinks), feather
+ * f >= 0 (pixels), profile (INSV2V_MASK_PROFILE_*).  Per frame:
+ *   inside   = m > tau (strict; a NaN is outside)
+ *   D2_out(x) = the squared Euclidean distance from x to the nearest inside pixel of the frame (0 on inside pixels);
+ *   D2_in(x)  = the same to the nearest outside pixel (0 on outside pixels).  Both are integers.  The frame border is NOT outside: a
+ *               mask that touches it stays full up to it.  R = ceil(max(g + f, 1 - g, 1)) is the smallest search radius that decides
+ *               every pixel; every D2 > R^2 - also that of a frame without any inside (outside) pixel - is FAR = (R + 1)^2.
+ *   s(x)     = sqrt(D2_out) on outside pixels (>= 1),  1 - sqrt(D2_in) on inside pixels (<= 0): the signed distance to the edge
+ *   shaped   = 1 where s <= g;  else 0 where s >= g + f;  else, with u = (g + f - s) / f, u (linear) or u^2 (3 - 2 u) (smooth), kept
+ *              inside [2^-126, 1 - 2^-24] so that a ramp value is never exactly 0 or 1.  The feather lies OUTSIDE the grown edge.
+ *   support  = 1 where shaped > 0, else 0.
+ * The two hard decisions are taken on integers: D2 against the four thresholds of insv2v_mask_shape_plan, which are the comparisons on
+ * s in float64 turned into integers (floor(g^2), ceil((g + f)^2) and their mirrors (1 - g)^2, (1 - g - f)^2 wherever those squares are
+ * exact).  So exactly 1, exactly 0 and support are exact; only the ramp is floating point - fp32, in this order: s from sqrtf of the
+ * integer, u = (gf - s) / f with gf = g + f formed in double and rounded once, then u * u * (3 - 2 u).
+ * Limits: -32 <= g <= 32, 0 <= f <= 32, g + f >= -32 (INSV2V_MASK_SHAPE_MAX), so R <= 64.
+ * Two launches: a column pass writes, per pixel, the capped vertical distance to the nearest inside / outside pixel of its column into
+ * the workspace (one signed byte), a row pass takes min over |dx| <= R of dx^2 + v(x + dx)^2 in int32 from LDS, decides and stores.
+ * Every thread writes its own pixels with plain stores: no atomics, two calls give the same bits.  Nothing is allocated: the caller
+ * passes workspace (4-byte aligned) of at least insv2v_mask_shape_workspace_bytes(T,H,W) bytes.  d2_out / d2_in (NULL = not written)
+ * return the two integer maps.
+ * INSV2V_EINVAL, nothing launched and no output touched: a NULL descriptor, m, shaped, support or workspace; T, H or W < 1, or more row
+ * tiles than a grid holds; g or f outside the limits or not finite; tau not finite; a profile outside {0, 1}; a workspace that is too
+ * small or misaligned; an output (shaped, support, d2_out, d2_in, workspace) that overlaps m or another output.
+ */
+#define INSV2V_MASK_SHAPE_MAX 32
+#define INSV2V_MASK_PROFILE_LINEAR 0
+#define INSV2V_MASK_PROFILE_SMOOTH 1
+typedef struct insv2v_mask_shape_plan_t {
+    int32_t rc;          /* 0, or INSV2V_EINVAL for (grow, feather) the entry refuses: every other field is then meaningless */
+    int32_t R;           /* search radius */
+    int32_t far;         /* (R + 1)^2 */
+    int32_t out_one;     /* outside pixel: shaped = 1  iff D2_out <= out_one   (-1: never) */
+    int32_t out_zero;    /*                shaped = 0  iff D2_out >= out_zero, checked after out_one */
+    int32_t in_one;      /* inside pixel:  shaped = 1  iff D2_in >= in_one */
+    int32_t in_zero;     /*                shaped = 0  iff D2_in <= in_zero    (-1: never), checked after in_one */
+    int32_t row_tile;    /* pixels of a row one workgroup of the row pass owns: what the tests place their blobs by */
+} insv2v_mask_shape_plan_t;
+/* Host-only, launches nothing; returns out->rc (INSV2V_EINVAL also for out == NULL). */
+int insv2v_mask_shape_plan(float grow, float feather, insv2v_mask_shape_plan_t* out);
+typedef struct insv2v_mask_shape_desc {
+    const float* m;        /* [T,H,W] */
+    float* shaped;         /* [T,H,W] */
+    float* support;        /* [T,H,W] */
+    int32_t* d2_out;       /* [T,H,W] or NULL */
+    int32_t* d2_in;        /* [T,H,W] or NULL */
+    void* workspace;
+    int64_t workspace_bytes;
+    int32_t T, H, W;
+    float threshold, grow, feather;
+    int32_t profile;
+} insv2v_mask_shape_desc;
+/* Bytes of workspace for a [T,H,W] mask; INSV2V_EINVAL for a size the entry refuses. */
+int64_t insv2v_mask_shape_workspace_bytes(int32_t T, int32_t H, int32_t W);
+int insv2v_mask_shape(const insv2v_mask_shape_desc* d, insv2v_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -179,6 +179,20 @@ class TemporalFilterDesc(C.Structure):
                 ("K", c_i32), ("T", c_i32), ("H", c_i32), ("W", c_i32), ("sigma", c_f32), ("strength", c_f32)]
 
 
+MASK_SHAPE_MAX, MASK_PROFILES = 32, ("linear", "smooth")   # INSV2V_MASK_SHAPE_MAX, INSV2V_MASK_PROFILE_* in their order
+
+
+class MaskShapePlan(C.Structure):
+    """insv2v_mask_shape_plan_t: what insv2v_mask_shape does with (grow, feather) (insv2v_mask_shape_plan; csrc/mask_shape_plan.h)."""
+    _fields_ = [(n, c_i32) for n in ("rc", "R", "far", "out_one", "out_zero", "in_one", "in_zero", "row_tile")]
+
+
+class MaskShapeDesc(C.Structure):
+    """insv2v_mask_shape_desc (csrc/mask_shape.hip)."""
+    _fields_ = [("m", c_p), ("shaped", c_p), ("support", c_p), ("d2_out", c_p), ("d2_in", c_p), ("workspace", c_p), ("workspace_bytes", c_i64),
+                ("T", c_i32), ("H", c_i32), ("W", c_i32), ("threshold", c_f32), ("grow", c_f32), ("feather", c_f32), ("profile", c_i32)]
+
+
 # name -> (restype, argtypes); mirrors include/insv2v_hip.h one to one.
 SIGNATURES = {
     "insv2v_abi_version": (c_i32, []),
@@ -251,6 +265,9 @@ SIGNATURES = {
     "insv2v_frame_fidelity": (c_i32, [C.POINTER(FidelityDesc), c_p]),
     "insv2v_frame_fidelity_tile": (c_i32, [C.POINTER(c_i32), C.POINTER(c_i32)]),
     "insv2v_temporal_filter": (c_i32, [C.POINTER(TemporalFilterDesc), c_p]),
+    "insv2v_mask_shape_plan": (c_i32, [c_f32, c_f32, C.POINTER(MaskShapePlan)]),
+    "insv2v_mask_shape_workspace_bytes": (c_i64, [c_i32, c_i32, c_i32]),
+    "insv2v_mask_shape": (c_i32, [C.POINTER(MaskShapeDesc), c_p]),
 }
 
 _lib = None

@@ -1333,3 +1333,49 @@ def temporal_filter(edited, guide, flow, valid, offsets, *, sigma=0.1, strength=
     d.K, d.T, d.H, d.W, d.sigma, d.strength = K, T, H, W, sigma, strength
     check(lib.insv2v_temporal_filter(_byref(d), _stream()), "insv2v_temporal_filter")
     return out
+
+
+# ----------------------------------------------------------------------------- shaping a mask (insv2v/mask_shape.py)
+def mask_shape_plan(grow, feather):
+    """insv2v_mask_shape_plan: the search radius, FAR and the four integer thresholds of (grow, feather) as a dict; launches nothing."""
+    p = _lib.MaskShapePlan()
+    check(_lib.load().insv2v_mask_shape_plan(grow, feather, _byref(p)), "insv2v_mask_shape_plan")
+    return {n: getattr(p, n) for n, _ in p._fields_ if n != "rc"}
+
+
+def mask_shape(mask, *, grow=0.0, feather=0.0, threshold=0.5, profile="smooth", return_d2=False, out=None, workspace=None):
+    """insv2v_mask_shape (tests/mask_shape_ref.py is the definition): ``mask`` fp32 [T,H,W] -> (shaped, support)
+    fp32 [T,H,W], and with ``return_d2`` also (d2_out, d2_in) int32 [T,H,W], the squared distances to the nearest inside / outside
+    pixel.  ``out``: those tensors preallocated (a 2- or 4-tuple); ``workspace``: a contiguous uint8 tensor of at least
+    insv2v_mask_shape_workspace_bytes(T,H,W) bytes (default: allocated here)."""
+    lib = _lib.load()
+    _req(mask, torch.float32, "mask_shape.mask")
+    if mask.dim() != 3 or not mask.is_contiguous():
+        raise _lib.HipKernelError(f"mask_shape: mask {tuple(mask.shape)} must be a contiguous [T,H,W]")
+    if profile not in _lib.MASK_PROFILES:
+        raise ValueError(f"mask_shape: profile {profile!r} is neither 'linear' nor 'smooth'")
+    T, H, W = mask.shape
+    if out is None:
+        out = tuple(torch.empty_like(mask) for _ in range(2))
+        if return_d2:
+            out += tuple(torch.empty(mask.shape, device=mask.device, dtype=torch.int32) for _ in range(2))
+    if len(out) != (4 if return_d2 else 2):
+        raise _lib.HipKernelError(f"mask_shape: out must hold {4 if return_d2 else 2} tensors")
+    for i, t in enumerate(out):
+        _plain(t, (T, H, W), f"mask_shape.out[{i}]", torch.float32 if i < 2 else torch.int32)
+    nbytes = lib.insv2v_mask_shape_workspace_bytes(T, H, W)
+    if nbytes <= 0:
+        raise _lib.HipKernelError(f"mask_shape: no workspace size for mask {tuple(mask.shape)}")
+    if workspace is None:
+        workspace = torch.empty(nbytes, device=mask.device, dtype=torch.uint8)
+    else:
+        _req(workspace, torch.uint8, "mask_shape.workspace")
+        if not workspace.is_contiguous():
+            raise _lib.HipKernelError("mask_shape: the workspace must be contiguous")
+    d = _lib.MaskShapeDesc()
+    d.m, d.shaped, d.support = mask.data_ptr() or None, out[0].data_ptr() or None, out[1].data_ptr() or None
+    d.d2_out, d.d2_in = (out[2].data_ptr() or None, out[3].data_ptr() or None) if return_d2 else (None, None)
+    d.workspace, d.workspace_bytes = workspace.data_ptr() or None, workspace.numel()
+    d.T, d.H, d.W, d.threshold, d.grow, d.feather, d.profile = T, H, W, threshold, grow, feather, _lib.MASK_PROFILES.index(profile)
+    check(lib.insv2v_mask_shape(_byref(d), _stream()), "insv2v_mask_shape")
+    return tuple(out)

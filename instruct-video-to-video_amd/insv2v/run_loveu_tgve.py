@@ -16,7 +16,9 @@ with CLIP on the HIP kernels (``insv2v/clip_score.py``: the reference's ``ClipSi
 
 Masks: drawn per frame or still (``mask=``, the "mask" entry of a ``--units`` file, ``--mask-file``), estimated from the prompt
 (``mask="auto"``, ``--auto-mask``), or drawn on one frame and tracked through the video with optical flow (``mask_key=``, ``--mask-key``:
-``insv2v/mask_track.py``).
+``insv2v/mask_track.py``); ``--mask-image`` reads a drawn mask from a PNG or a folder of PNGs (``video_io.load_mask``).  ``mask_shape=`` /
+``--mask-grow`` / ``--mask-feather`` grows, shrinks and feathers the mask of any of these sources, once per unit (``insv2v/mask_shape.py``,
+DESIGN.md section 22): the composite gets the soft mask, the latent hold the hard region under it.
 
 ``stabilize=`` / ``--stabilize`` filters a unit's decoded frames along the SOURCE video's optical flow, once per unit and after its last
 window (``insv2v/temporal_filter.py``): the switch to pull when ``--score-warp`` shows flicker.
@@ -67,7 +69,7 @@ STABILIZE_KEYS = ("radius", "sigma", "strength", "occlusion", "alpha", "beta")
 
 
 def check_edit_args(frames_shape, mask=None, strength=1.0, mask_mode="max", auto_mask=None, mask_key=None, mask_flows=None, mask_track=None,
-                    stabilize=None, stabilize_flows=None):
+                    stabilize=None, stabilize_flows=None, mask_shape=None):
     """Host-side check of the localized / partial edit controls (nothing is launched): ``strength`` in (0, 1], ``mask_mode`` "mean" or
     "max", ``mask`` a floating-point [1,T,H,W] or [1,1,H,W] tensor for frames [1,T,3,H,W] with H and W multiples of 8 - or the string
     "auto" (the mask is estimated from the prompt, ``InferenceIP2PVideo.estimate_mask``), then optionally with ``auto_mask``, a dict of
@@ -75,8 +77,14 @@ def check_edit_args(frames_shape, mask=None, strength=1.0, mask_mode="max", auto
     and tracked through the video, ``insv2v/mask_track.py``) optionally with ``mask_flows``, a dict(fwd=, bwd=) of [T-1,2,H,W] flows, and
     ``mask_track``, a dict of ``propagate_mask``'s keywords (``MASK_TRACK_KEYS``).  ``stabilize`` (None, True or a dict of
     ``temporal_filter.stabilize``'s parameters, ``STABILIZE_KEYS``) optionally with ``stabilize_flows``, a dict(fwd=, bwd=) of the source
-    video's [T-1,2,H,W] flows."""
+    video's [T-1,2,H,W] flows.  ``mask_shape`` (None or a dict of ``mask_shape.check_shape_args``' parameters, ``MASK_SHAPE_KEYS``) shapes
+    the mask of any source, so it needs one."""
     strength_to_start(strength, 1)
+    if mask_shape is not None:
+        from .mask_shape import check_mask_shape
+        check_mask_shape(mask_shape)
+        if mask is None:
+            raise ValueError("mask_shape shapes the mask of a localized edit: pass mask= (a tensor, \"auto\", or with mask_key=) with it")
     _check_stabilize_args(frames_shape, stabilize, stabilize_flows)
     if mask_key is None and (mask_flows is not None or mask_track is not None):
         raise ValueError("mask_flows / mask_track belong to a tracked mask: pass mask_key=, the frame the mask is drawn on, with them")
@@ -180,12 +188,12 @@ class _EditPlan:
     latent-resolution mask, split like ``cond``, and the level the trajectory starts from.  ``active`` is False for a plain edit, whose
     calls then carry no new keyword."""
 
-    def __init__(self, model, inf_pipe, frames, cond, mask, strength, mask_mode, frames_in_batch, num_ref_frames, z=None):
+    def __init__(self, model, inf_pipe, frames, cond, mask, strength, mask_mode, frames_in_batch, num_ref_frames, z=None, mask_shape=None):
         dev = model.unet.device
         self.start_time = _start_time(inf_pipe, strength)
         partial = strength != 1.0   # (also a strength below 1 that rounds to every step: it starts from the noised source at timesteps[0])
         self.active = mask is not None or partial
-        self.mask_img = self.masks = self.level = None
+        self.mask_img = self.masks = self.level = self.shape = None
         if not self.active:
             return
         if z is None:   # (a caller's ``cond`` is z / scale_factor)
@@ -196,7 +204,14 @@ class _EditPlan:
         if mask is not None:
             T = frames.shape[1]
             self.mask_img = mask.to(device=dev, dtype=torch.float32).expand(1, T, *mask.shape[2:])[0].contiguous()   # [T,H,W]
-            self.masks = split_batch(ops.mask_to_latent(self.mask_img, mask_mode)[None], frames_in_batch, num_ref_frames)[0]   # reduced ONCE
+            if mask_shape is None:
+                latent_mask = ops.mask_to_latent(self.mask_img, mask_mode)
+            else:   # two masks: the soft one for the composite, the hard region under it - the whole feather - for the latent hold
+                from .mask_shape import shape_mask
+                self.mask_img, support = shape_mask(self.mask_img, **mask_shape)
+                self.shape = dict(shaped=self.mask_img[None], support=support[None])
+                latent_mask = ops.mask_to_latent(support, "max")
+            self.masks = split_batch(latent_mask[None], frames_in_batch, num_ref_frames)[0]   # reduced ONCE
 
     def window(self, k, R, init):
         """(initial latent, extra keywords) of window k, whose first R frames are carried over; ``init`` = the window's initial noise."""
@@ -274,6 +289,12 @@ def _stabilize(frames, image, params, flows, mask_img):
     return stabilize(frames, image, flows=flows, mask=None if mask_img is None else mask_img[None], **params)
 
 
+def _with_shape(est, plan):
+    """``return_mask``'s dict of a unit: with ``mask_shape`` it gains ``shaped`` and ``support`` [1,T,H,W] (a drawn mask has no dict
+    before that)."""
+    return est if plan.shape is None else dict(est or {}, **plan.shape)
+
+
 def _result(image, latent, est, return_latent, return_mask):
     out = (image,) + ((latent,) if return_latent else ()) + ((est,) if return_mask else ())
     return out if len(out) > 1 else image
@@ -283,7 +304,7 @@ def _result(image, latent, est, return_latent, return_mask):
 def edit_video(model, inf_pipe, frames, text_cond, text_uncond, text_cfg=7.5, video_cfg=1.8, frames_in_batch=16,
                num_ref_frames=4, init_noises=None, enc_noise=None, flows_per_window=None, return_latent=False, cond=None,
                seed=None, unit=0, mask=None, strength=1.0, mask_mode="max", auto_mask=None, return_mask=False,
-               mask_key=None, mask_flows=None, flow_estimator=None, mask_track=None, stabilize=None, stabilize_flows=None):
+               mask_key=None, mask_flows=None, flow_estimator=None, mask_track=None, stabilize=None, stabilize_flows=None, mask_shape=None):
     """frames [1,T,3,H,W] in [-1,1] -> edited frames [1,T,3,H,W] clipped to [-1,1].
 
     ``seed`` (default None: every draw comes from the global torch generators, as before) makes the edit reproducible: the posterior
@@ -325,8 +346,15 @@ def edit_video(model, inf_pipe, frames, text_cond, text_uncond, text_cfg=7.5, vi
     window hands over to the next; the result returned (and scored) is the filtered one, composited against the input under a mask like
     the edit itself.  The flows are ``stabilize_flows`` (dict(fwd=, bwd=) of [T-1,2,H,W]), else the ``mask_flows`` of a tracked mask, else
     computed by ``flow_estimator`` (default: the pipe's own) - once per unit: a tracked mask and the filter share one
-    ``pair_flows(both=True)``.  Without ``stabilize`` nothing of this runs."""
-    check_edit_args(frames.shape, mask, strength, mask_mode, auto_mask, mask_key, mask_flows, mask_track, stabilize, stabilize_flows)
+    ``pair_flows(both=True)``.  Without ``stabilize`` nothing of this runs.
+
+    ``mask_shape`` (a dict with keys among ``MASK_SHAPE_KEYS``: ``grow`` and ``feather`` in pixels, ``threshold``, ``profile``; DESIGN.md
+    section 22) shapes the unit's mask - drawn, ``"auto"`` or tracked - once, before the first window: the composite (and ``stabilize``'s)
+    uses ``shaped``, the mask grown by ``grow`` and feathered over ``feather`` pixels outside the grown edge; the latent hold uses
+    ``support``, the hard region ``shaped > 0``, reduced with "max" - so ``mask_mode`` has no effect when ``mask_shape`` is given.  Outside
+    ``support`` the pixels are the input's bit for bit.  ``return_mask=True`` then returns a dict that also holds ``shaped`` and
+    ``support`` [1,T,H,W] (for a drawn mask: only those).  Without ``mask_shape`` nothing of this runs."""
+    check_edit_args(frames.shape, mask, strength, mask_mode, auto_mask, mask_key, mask_flows, mask_track, stabilize, stabilize_flows, mask_shape)
     dev = model.unet.device
     est = None
     stab, sflows = _stabilize_params(stabilize), None
@@ -345,7 +373,8 @@ def edit_video(model, inf_pipe, frames, text_cond, text_uncond, text_cfg=7.5, vi
         est = _estimate_mask(model, inf_pipe, z, cond, text_cond, text_uncond, frames_in_batch, auto_mask, seed, unit)
         mask = est["mask"]
     conds, refs = split_batch(cond, frames_in_batch, num_ref_frames)
-    plan = _EditPlan(model, inf_pipe, frames, cond, mask, strength, mask_mode, frames_in_batch, num_ref_frames, z=z)
+    plan = _EditPlan(model, inf_pipe, frames, cond, mask, strength, mask_mode, frames_in_batch, num_ref_frames, z=z, mask_shape=mask_shape)
+    est = _with_shape(est, plan)
     frame_chunks, _ = split_batch(frames, frames_in_batch, num_ref_frames)
     rng = _seeded(seed, unit)
     wants_flow = hasattr(inf_pipe, "obtain_flow_batched")
@@ -409,19 +438,21 @@ def edit_videos(model, inf_pipe, units, frames_in_batch=16, num_ref_frames=4, re
     tracked alone, before the stacked windows start, bit for bit as ``edit_video`` tracks it; ``flow_estimator`` is the flow source of
     the units without ``mask_flows`` (default: the pipe's own).  Tracked, drawn, auto and unmasked units stack together.  A unit may carry
     ``stabilize`` (and ``stabilize_flows``) as for ``edit_video``: it is filtered alone, after the stacked windows have finished, bit for
-    bit as ``edit_video`` filters it; stabilized and plain units stack together."""
+    bit as ``edit_video`` filters it; stabilized and plain units stack together.  A unit may carry ``mask_shape`` as for ``edit_video``: its
+    mask is shaped alone, before the stacked windows start, bit for bit as ``edit_video`` shapes it."""
     if len(units) == 0:
         return []
     for u in units:
         check_edit_args(u["frames"].shape, u.get("mask"), u.get("strength", 1.0), u.get("mask_mode", "max"), u.get("auto_mask"),
-                        u.get("mask_key"), u.get("mask_flows"), u.get("mask_track"), u.get("stabilize"), u.get("stabilize_flows"))
+                        u.get("mask_key"), u.get("mask_flows"), u.get("mask_track"), u.get("stabilize"), u.get("stabilize_flows"),
+                        u.get("mask_shape"))
     if len({_start_time(inf_pipe, u.get("strength", 1.0)) for u in units}) > 1:
         raise ValueError("edit_videos: the units of one call must share the number of executed steps (strength); edit the others separately")
     wants_flow = hasattr(inf_pipe, "obtain_flow_batched")
     ids = [u.get("unit", j) for j, u in enumerate(units)]
     if len(units) == 1:
         keys = ("text_cfg", "video_cfg", "init_noises", "enc_noise", "cond", "flows_per_window", "mask", "strength", "mask_mode", "auto_mask",
-                "mask_key", "mask_flows", "mask_track", "stabilize", "stabilize_flows")
+                "mask_key", "mask_flows", "mask_track", "stabilize", "stabilize_flows", "mask_shape")
         more = {"return_mask": True} if return_mask else {}   # (a plain call carries no new keyword)
         if flow_estimator is not None:
             more["flow_estimator"] = flow_estimator
@@ -453,7 +484,8 @@ def edit_videos(model, inf_pipe, units, frames_in_batch=16, num_ref_frames=4, re
             est = _estimate_mask(model, inf_pipe, z, cond, u["text_cond"], u["text_uncond"], frames_in_batch, u.get("auto_mask"), seed, uid)
             mask = est["mask"]
         plan = _EditPlan(model, inf_pipe, u["frames"], cond, mask, u.get("strength", 1.0), u.get("mask_mode", "max"),
-                         frames_in_batch, num_ref_frames, z=z)
+                         frames_in_batch, num_ref_frames, z=z, mask_shape=u.get("mask_shape"))
+        est = _with_shape(est, plan)
         if wants_flow and u.get("flows_per_window") is None and getattr(inf_pipe, "flow_estimator", None) is None and len(conds) > 1:
             raise RuntimeError("optical-flow pipeline without a flow source: pass flows_per_window= or build the pipe with flow_estimator=")
         st.append(dict(u=u, unit=uid, conds=conds, refs=refs, preds=[], init=None, pred=None, plan=plan, est=est, stab=stab, sflows=sflows,
@@ -551,10 +583,21 @@ def build_parser():
     p.add_argument("--auto-mask-threshold", type=float, default=0.5, help="in (0, 1): a cell is edited where the normalised map exceeds it")
     p.add_argument("--auto-mask-dilate", type=int, default=1, help="latent cells the thresholded mask is grown by")
     p.add_argument("--mask-out", type=str, default=None,
-                   help=".pt file for the masks this run computed: {unit id: {mask_latent, soft}} with --auto-mask, {unit id: {mask, valid}} with --mask-key")
+                   help=".pt file for the masks this run computed: {unit id: {mask_latent, soft}} with --auto-mask, {unit id: {mask, valid}} with --mask-key; "
+                        "with --mask-grow / --mask-feather each also holds the shaped mask and its support")
     p.add_argument("--mask-file", type=str, default=None,
                    help=".pt file with drawn masks: {unit id or video name: tensor [1,1,H,W] or [1,T,H,W]} (image resolution; units it does not "
                         "name are edited whole)")
+    p.add_argument("--mask-image", type=str, default=None,
+                   help="a drawn mask from image files: one image (a still mask for every frame) or a directory of images sorted by name (one "
+                        "per frame); read as 8-bit grey, white = edit, resized like the frames; every unit gets it")
+    p.add_argument("--mask-grow", type=float, default=None,
+                   help="shape every unit's mask (drawn, tracked or estimated; insv2v/mask_shape.py): grow it by F pixels, negative shrinks, "
+                        "[-32, 32]; the --mask-grow / --mask-feather / --mask-profile / --mask-threshold values are starting points, untuned")
+    p.add_argument("--mask-feather", type=float, default=None,
+                   help="feather the mask over F pixels OUTSIDE its (grown) edge, [0, 32]: the composite blends there, the latent is free there")
+    p.add_argument("--mask-profile", type=str, default=None, help="linear | smooth (default): the feather's ramp")
+    p.add_argument("--mask-threshold", type=float, default=None, help="a pixel is inside the mask where its value exceeds this (default 0.5)")
     p.add_argument("--mask-key", type=int, default=None,
                    help="the frame the masks are drawn on ([1,1,H,W] each): they follow the motion through the video (insv2v/mask_track.py); the "
                         "flows come from the estimator of --raft-ckpt (--synthetic: key-hashed weights)")
@@ -614,17 +657,31 @@ def check_args(args):
     if getattr(args, "auto_mask", False) and getattr(args, "synthetic_mask", False):
         raise SystemExit("--auto-mask and --synthetic-mask are two masks: pass one")
     mask_key, mask_file = getattr(args, "mask_key", None), getattr(args, "mask_file", None)
-    if getattr(args, "mask_out", None) and not getattr(args, "auto_mask", False) and mask_key is None:
+    mask_image, shaping = getattr(args, "mask_image", None), bool(mask_shape_unit(args))
+    if getattr(args, "mask_out", None) and not getattr(args, "auto_mask", False) and mask_key is None and not shaping:
         raise SystemExit("--mask-out holds the masks a run computes: it needs --auto-mask or --mask-key")
     if mask_file and (getattr(args, "auto_mask", False) or getattr(args, "synthetic_mask", False)):
         raise SystemExit("--mask-file next to --auto-mask / --synthetic-mask are two masks: pass one")
+    if mask_image and (mask_file or getattr(args, "auto_mask", False) or getattr(args, "synthetic_mask", False)):
+        raise SystemExit("--mask-image next to --mask-file / --auto-mask / --synthetic-mask are two masks: pass one")
+    if mask_image and not os.path.exists(mask_image):
+        raise SystemExit(f"--mask-image {mask_image} is neither a file nor a directory")
+    if shaping:
+        from .mask_shape import check_shape_args
+        try:
+            check_shape_args(**mask_shape_unit(args)["mask_shape"])
+        except ValueError as e:
+            raise SystemExit(f"--mask-grow / --mask-feather / --mask-profile / --mask-threshold: {e}")
+        if not (mask_file or mask_image or getattr(args, "auto_mask", False) or getattr(args, "synthetic_mask", False) or args.units):
+            raise SystemExit("--mask-grow / --mask-feather / --mask-profile / --mask-threshold shape a mask: they need --mask-file, --mask-image, "
+                             "--auto-mask, --synthetic-mask or the \"mask\" entry of a --units file")
     if mask_key is not None:
         if getattr(args, "auto_mask", False):
             raise SystemExit("--mask-key tracks a drawn mask and --auto-mask estimates one per frame: pass one")
         if mask_key < 0:
             raise SystemExit(f"--mask-key must be a frame index, not {mask_key}")
-        if not (mask_file or getattr(args, "synthetic_mask", False) or args.units):
-            raise SystemExit("--mask-key needs a mask to track: --mask-file FILE.pt, the \"mask\" entry of a --units file, or --synthetic-mask")
+        if not (mask_file or mask_image or getattr(args, "synthetic_mask", False) or args.units):
+            raise SystemExit("--mask-key needs a mask to track: --mask-file FILE.pt, --mask-image PATH, the \"mask\" entry of a --units file, or --synthetic-mask")
         if not (args.raft_ckpt or args.synthetic):
             raise SystemExit("--mask-key needs --raft-ckpt FILE (torchvision raft_large weights): the flows the mask follows come from that estimator")
     elif getattr(args, "mask_no_occlusion", False):
@@ -738,6 +795,29 @@ def stabilize_unit(args):
                                occlusion=not getattr(args, "stabilize_no_occlusion", False)))
 
 
+def mask_shape_unit(args):
+    """What --mask-grow / --mask-feather / --mask-profile / --mask-threshold add to every unit that has a mask (nothing without any of
+    them): only the values given, the others keep ``check_shape_args``' defaults."""
+    given = {k: getattr(args, "mask_" + k, None) for k in ("grow", "feather", "profile", "threshold")}
+    given = {k: v for k, v in given.items() if v is not None}
+    return dict(mask_shape=given) if given else {}
+
+
+def load_mask_image(args, width, height):
+    """The mask of --mask-image at the frames' size ([1,1,H,W] or [1,T,H,W]; None without it)."""
+    if not getattr(args, "mask_image", None):
+        return None
+    from .video_io import load_mask
+    return load_mask(args.mask_image, (width, height))
+
+
+def mask_region(est, drawn):
+    """The region --score-pixels splits a unit by: the shaped mask if the run shaped one, else the tracked / estimated one, else as drawn."""
+    if est is not None:
+        return est["shaped"] if "shaped" in est else est["mask"]
+    return drawn
+
+
 def load_mask_file(args):
     """{unit id or video name: mask tensor} of --mask-file ({} without it)."""
     if not getattr(args, "mask_file", None):
@@ -762,8 +842,17 @@ def build_flow_estimator(args, device):
 
 def write_masks(path, records, rank=0, world=1):
     """{unit id: {"mask_latent": [T,h,w], "soft": [T,h,w]}} (estimated, --auto-mask) or {unit id: {"mask": [T,H,W], "valid": [T,H,W]}}
-    (tracked, --mask-key) of this rank's units (with several ranks each writes its own FILE.rankR.pt)."""
+    (tracked, --mask-key) of this rank's units (with several ranks each writes its own FILE.rankR.pt).  A shaped run (--mask-grow /
+    --mask-feather) writes every unit's "shaped" and "support" [T,H,W] next to whatever its source returned."""
     records = {u: est for u, est in records.items() if est is not None}   # (a unit the mask file does not name has none)
+    if any("shaped" in est for est in records.values()):   # --mask-grow / --mask-feather: what the source gave, and the two shaped masks
+        if world > 1:
+            root, ext = os.path.splitext(path)
+            path = f"{root}.rank{rank}{ext}"
+        os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
+        keys = ("mask", "valid", "mask_latent", "soft", "shaped", "support")
+        torch.save({int(u): {k: (est[k] if k == "valid" else est[k][0]).cpu() for k in keys if k in est} for u, est in sorted(records.items())}, path)
+        return
     if any("valid" in est for est in records.values()):
         if world > 1:
             root, ext = os.path.splitext(path)
@@ -814,9 +903,9 @@ def run_dataset(args, model, pipe, rank=0, world=1, scorer=None):
     auto = auto_mask_unit(args)
     track, drawn = mask_track_unit(args), load_mask_file(args)   # drawn masks are named by video here
     estimator = build_flow_estimator(args, model.unet.device)
-    stab = stabilize_unit(args)
+    stab, shape = stabilize_unit(args), mask_shape_unit(args)
     more = {"flow_estimator": estimator} if track or stab else {}
-    want_masks = {"return_mask": True} if (auto or track) and (getattr(args, "mask_out", None) or getattr(args, "score_pixels", False)) else {}   # (a plain run carries no new keyword)
+    want_masks = {"return_mask": True} if (auto or track or shape) and (getattr(args, "mask_out", None) or getattr(args, "score_pixels", False)) else {}   # (a plain run carries no new keyword)
     masks = {}
     for ci, (video_id, text_cfg, video_cfg, num_frames, image_size) in enumerate(combos):
         if ci % world != rank:
@@ -826,6 +915,8 @@ def run_dataset(args, model, pipe, rank=0, world=1, scorer=None):
         skip = n // num_frames if n > num_frames else 1
         frames = batch["frames"][::skip].to(model.unet.device)[None]
         text_uncond = model.encode_text([""])
+        if getattr(args, "mask_image", None):   # every video gets the image's mask, at this combination's frame size
+            drawn = {batch["video_name"]: load_mask_image(args, image_size, image_size)}
         cond = model.encode_image_to_latent(frames, **_seeded(seed, 4 * ci)) / model.scale_factor  # once per video, shared by the four prompts (:98)
         todo = []
         for key in kinds:
@@ -838,6 +929,7 @@ def run_dataset(args, model, pipe, rank=0, world=1, scorer=None):
             todo.append((gif_path, image_dir, dict(frames=frames, text_cond=model.encode_text([prompt]), text_uncond=text_uncond,
                                                    text_cfg=text_cfg, video_cfg=video_cfg, cond=cond, unit=4 * ci + kinds.index(key),
                                                    strength=getattr(args, "strength", 1.0), **auto, **stab,
+                                                   **(shape if auto or batch["video_name"] in drawn else {}),
                                                    **(dict(mask=drawn[batch["video_name"]], mask_mode=getattr(args, "mask_mode", "max"),
                                                            **track) if batch["video_name"] in drawn else {})), prompt))
         # the four prompts of a video share the conditioning latent and the window plan: one stacked launch chain per window (B = 12)
@@ -853,7 +945,7 @@ def run_dataset(args, model, pipe, rank=0, world=1, scorer=None):
                 rec.update(score_record(scorer, u["unit"], frames, edited, batch["original"], prompt))
             if want_pixel_scores(args):   # the region: the unit's image-resolution mask - tracked or estimated if the run made one, else as drawn
                 est = masks.get(u["unit"])
-                rec.update(pixel_record(args, frames, edited, est["mask"] if est is not None else u.get("mask"), estimator))
+                rec.update(pixel_record(args, frames, edited, mask_region(est, u.get("mask")), estimator))
             records.append(rec)
             save_tensor_to_gif(torch.cat([frames.float().cpu(), edited.float().cpu()], dim=4), gif_path, fps=5)
             save_tensor_to_images(edited.float().cpu(), image_dir)
@@ -929,20 +1021,22 @@ def main(argv=None):
     item_shape = tuple(data["frames"].shape[1:])  # a rank without units still takes part in the all_gather
     auto = auto_mask_unit(args, data)   # (refuses --auto-mask next to a "mask" entry of the file)
     track, drawn = mask_track_unit(args), load_mask_file(args)   # drawn masks are named by unit here
-    if drawn and data.get("mask") is not None:
-        raise SystemExit("--mask-file next to the \"mask\" entry of the --units file are two masks: pass one")
-    if track and not drawn and data.get("mask") is None:
+    image_mask = load_mask_image(args, data["frames"].shape[-1], data["frames"].shape[-2])   # every unit gets it
+    if (drawn or image_mask is not None) and data.get("mask") is not None:
+        raise SystemExit("--mask-file / --mask-image next to the \"mask\" entry of the --units file are two masks: pass one")
+    if track and not drawn and image_mask is None and data.get("mask") is None:
         raise SystemExit("--mask-key needs a mask to track: --mask-file FILE.pt, the \"mask\" entry of a --units file, or --synthetic-mask")
     estimator = build_flow_estimator(args, f"cuda:{local}")
-    stab = stabilize_unit(args)
+    stab, shape = stabilize_unit(args), mask_shape_unit(args)
     more = {"flow_estimator": estimator} if track or stab else {}
-    want_masks = {"return_mask": True} if (auto or track) and (args.mask_out or args.score_pixels) else {}
+    want_masks = {"return_mask": True} if (auto or track or shape) and (args.mask_out or args.score_pixels) else {}
     est_masks = {}
     masks = data.get("mask")   # optional [n,T,H,W] / [n,1,H,W]
 
     def edit(i):
-        m = masks[i:i + 1] if masks is not None else drawn.get(i)
-        return dict(dict(mask=m, strength=args.strength, mask_mode=args.mask_mode), **auto, **stab, **(track if m is not None else {}))
+        m = masks[i:i + 1] if masks is not None else drawn.get(i, image_mask)
+        return dict(dict(mask=m, strength=args.strength, mask_mode=args.mask_mode), **auto, **stab, **(track if m is not None else {}),
+                    **(shape if m is not None or auto else {}))
     scorer = build_scorer(args, f"cuda:{local}", tok)
     records = []
     outs = []
@@ -974,7 +1068,7 @@ def main(argv=None):
                 rec.update(score_record(scorer, ci * n + i, data["frames"][i:i + 1], edited, *_score_texts(data, i, scorer)))
             if want_pixel_scores(args):   # the region: the unit's image-resolution mask - tracked or estimated if the run made one, else as drawn
                 est = est_masks.get(ci * n + i)
-                rec.update(pixel_record(args, data["frames"][i:i + 1], edited, est["mask"] if est is not None else edit(i)["mask"], estimator))
+                rec.update(pixel_record(args, data["frames"][i:i + 1], edited, mask_region(est, edit(i)["mask"]), estimator))
             records.append(rec)
         local_out = torch.cat(local_out, 0).half() if local_out else torch.zeros((0, *item_shape), device=model.unet.device).half()
         outs.append(gather_frames(local_out, n, item_shape=item_shape))

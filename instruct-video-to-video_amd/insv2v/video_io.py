@@ -101,6 +101,24 @@ class LoveuTgveVideoDataset:
         return item
 
 
+def load_mask(path, image_size):
+    """A mask from image files: ``path`` is one image -> [1,1,H,W] (a still mask for every frame), or a directory of images, sorted by
+    name -> [1,T,H,W] (one per frame).  Read as PIL mode "L" (8-bit grey; white = edit), resized to ``image_size`` = (W, H) with the
+    bilinear resize the frames get (``LoveuTgveVideoDataset.load_frames``) and divided by 255: float32 in [0, 1]."""
+    from PIL import Image
+    if os.path.isdir(path):
+        names = [os.path.join(path, n) for n in sorted(os.listdir(path)) if n.lower().endswith(_IMG_EXT)]
+        if not names:
+            raise FileNotFoundError(f"no mask image ({', '.join(_IMG_EXT)}) in {path}")
+    elif os.path.isfile(path):
+        names = [path]
+    else:
+        raise FileNotFoundError(f"mask image {path} is neither a file nor a directory")
+    size = tuple(int(s) for s in image_size)
+    planes = [torch.from_numpy(np.array(Image.open(n).convert("L").resize(size, Image.BILINEAR), dtype=np.uint8)).float() / 255.0 for n in names]
+    return torch.stack(planes, dim=0)[None]
+
+
 def sampling_plan(video_fps, total_frames, sampling_fps=24, frame_gap=0, num_frames=2):
     """The frame-sampling arithmetic of SingleVideoDataset.__init__ (single_video_dataset.py:36-58), host integers only:
     returns (sampling_fps, frame_gap, frames per item, number of valid start frames).  ``sampling_fps`` may be an int, a list (the reference
