@@ -90,7 +90,8 @@ int insv2v_init(void);
  *   encoding added after the norm (motion_module.py:277-278) becomes the per-frame row_bias table
  *   pe @ W^T.  Removes the normalised copy of the activations from HBM (attention.py:236-259,
  *   motion_module.py:206,214).
- * Batched: grid y = batch, operands advanced by *_bs elements per batch.
+ * Batched: grid y = batch, operands advanced by *_bs elements per batch.  With k_split > 0 the second source `a2` advances by a_bs
+ *   elements too (there is no stride of its own), whatever lda2 is: its batches lie a_bs elements apart.
  * Split-K: when `workspace` is given (fp32 scratch of workspace_bytes) the library may split K over
  *   split_k workgroups per tile (0 = decide automatically: only for problems too small to fill the GPU
  *   with long K, e.g. the 4x6-latent UNet level) and reduce the fp32 partials in a second kernel that
