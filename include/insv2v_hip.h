@@ -316,6 +316,28 @@ typedef struct insv2v_rowlin_desc {
 } insv2v_rowlin_desc;
 int insv2v_rowlin(const insv2v_rowlin_desc* d, insv2v_stream_t stream);
 int64_t insv2v_rowlin_stream_elems(int32_t N, int32_t K);
+/* What insv2v_rowlin does with a descriptor, without doing it: the answer of the one planner (csrc/rows_plan.h) that insv2v_rowlin
+ * consults before it launches.  A pure function of the descriptor's integers, the null and alignment bits of its pointers, the CU count
+ * and the mask INSV2V_ROWLIN_TB2 (read once per process; bit `form` set: that K = 640 form may run two token blocks per wave); it touches
+ * no GPU.  rowlin_kernel<ks, LN, FRAME, RES, gn, token_blocks> is the kernel: 2 x 8 forms with one token block per wave, 8 at K = 640 with
+ * two (chosen where ceil(M / 256) >= 2 cus), and the GroupNorm-on-load form at both K.  A purely additive entry of ABI 15. */
+typedef struct insv2v_rowlin_plan_t {
+    int32_t rc;            /* 0, or what insv2v_rowlin returns without launching (INSV2V_EINVAL / INSV2V_EUNSUPPORTED) */
+    int32_t ks;            /* 20 (K = 320) or 40 (K = 640) */
+    int32_t form;          /* LN << 2 | FRAME << 1 | RES */
+    int32_t gn;            /* the GroupNorm-on-load kernel */
+    int32_t token_blocks;  /* TB: 1 or 2 */
+    int32_t tile_rows;     /* 128 * TB */
+    int32_t ntiles;        /* what the kernel loops over (gn: the 128-row tiles of the segmented schedule, four wave blocks each) */
+    int32_t grid;          /* workgroups: min(ntiles, cus * wgs_per_cu) */
+    int32_t rounds;        /* ceil(ntiles / grid): >= 2 means some workgroup takes a second tile */
+    int32_t wgs_per_cu;    /* 2 at K = 320, 1 at K = 640 */
+    int32_t lds_bytes;     /* dynamic LDS per workgroup */
+    int32_t gn_units;      /* gn: 32-row wave blocks per sample = ceil(gn_rows / 32) */
+} insv2v_rowlin_plan_t;
+/* cus <= 0: this device's CU count (without a GPU there is none, and a problem that is otherwise accepted gets rc = INSV2V_EINVAL, as the
+ * launch would).  Returns INSV2V_EINVAL for a NULL argument, else 0 with *out filled - also when out->rc says the problem is refused. */
+int insv2v_rowlin_plan(const insv2v_rowlin_desc* d, int32_t cus, insv2v_rowlin_plan_t* out);
 
 /*
  * insv2v_tattn_fused: one temporal self-attention sub-block of TemporalTransformerBlock (motion_module.py:206,270-336:

@@ -25,7 +25,7 @@ def build(force=False, verbose=True):
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     objdir = os.path.join(HERE, "build")
     os.makedirs(objdir, exist_ok=True)
-    deps = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "gemm_dma.h"), os.path.join(CSRC, "gemm_plan.h"), os.path.join(CSRC, "norm_plan.h"), os.path.join(CSRC, "attn_plan.h"), os.path.join(CSRC, "rows_common.h"), os.path.join(CSRC, "rng.h"), os.path.join(CSRC, "flow_sample.h"), os.path.join(CSRC, "mask_shape_plan.h"), os.path.join(HERE, "..", "include", "insv2v_hip.h")]
+    deps = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "gemm_dma.h"), os.path.join(CSRC, "gemm_plan.h"), os.path.join(CSRC, "norm_plan.h"), os.path.join(CSRC, "attn_plan.h"), os.path.join(CSRC, "rows_common.h"), os.path.join(CSRC, "rows_plan.h"),os.path.join(CSRC, "rng.h"), os.path.join(CSRC, "flow_sample.h"), os.path.join(CSRC, "mask_shape_plan.h"), os.path.join(HERE, "..", "include", "insv2v_hip.h")]
     jobs = []
     for src in SOURCES:
         s, o = os.path.join(CSRC, src), os.path.join(objdir, src + ".o")

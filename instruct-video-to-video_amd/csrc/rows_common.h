@@ -294,21 +294,28 @@ int launch_unit_ranges(int64_t units, int64_t unit_bytes, Fn&& launch, int64_t w
     return 0;
 }
 
+// `grid` persistent workgroups of 256 threads with `lds` bytes of dynamic LDS
 template <class Args>
-int launch_rows(const void* kernel, bool& attr_set, int lds, const Args& args, int M, hipStream_t s, int wgs_per_cu = 1) {
+int launch_grid(const void* kernel, bool& attr_set, int lds, const Args& args, int grid, hipStream_t s) {
     if (!attr_set) {
         hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
         if (e != hipSuccess) return (int)e;
         attr_set = true;
     }
-    const int ncu = num_cus() * wgs_per_cu;
-    if (ncu <= 0) return INSV2V_EINVAL;
-    const int ntiles = (M + 127) / 128;
+    if (grid <= 0) return INSV2V_EINVAL;
     Args a = args;
     void* kargs[] = {&a};
-    hipError_t le = hipLaunchKernel(kernel, dim3(ntiles < ncu ? ntiles : ncu), dim3(256), kargs, lds, s);
+    hipError_t le = hipLaunchKernel(kernel, dim3(grid), dim3(256), kargs, lds, s);
     if (le != hipSuccess) return (int)le;
     return launch_status();
+}
+
+// one workgroup per 128-row tile of M rows, at most wgs_per_cu per CU
+template <class Args>
+int launch_rows(const void* kernel, bool& attr_set, int lds, const Args& args, int M, hipStream_t s, int wgs_per_cu = 1) {
+    const int ncu = num_cus() * wgs_per_cu;
+    const int ntiles = (M + 127) / 128;
+    return launch_grid(kernel, attr_set, lds, args, ntiles < ncu ? ntiles : ncu, s);   // (no CU count: grid <= 0 is refused there)
 }
 
 }  // namespace

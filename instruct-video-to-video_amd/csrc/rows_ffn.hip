@@ -1,5 +1,6 @@
 // Fused feed-forward (insv2v_ffn_fused) and the K = 320 / 640 row Linear (insv2v_rowlin); the register-resident scheme: rows_common.h
 #include "rows_common.h"
+#include "rows_plan.h"
 #include <algorithm>
 #include <cstdlib>
 
@@ -271,8 +272,6 @@ struct RowLinArgs {
 //   [for k-step s = 0..KS: (tile 2p, tile 2p+1)] = 2 (KS + 1) fragments, then padding;  s = KS is the bias step
 //   K = 320: 42 fragments in 6 groups (3 slots); K = 640: 82 fragments in 12 groups (6 slots)
 constexpr int LIN_SLOT_FR = 16;
-// K = 640 forms that run two token blocks per wave: bit (LN << 2 | FRAME << 1 | RES); measured per form, profiles/r03_rowlin_tb2.txt
-constexpr int ROWLIN_TB2_DEFAULT = 0xff;
 template <int KS> struct LinCfg {
     static constexpr int FR = 2 * (KS + 1);                  // fragments of a pair
     static constexpr int GP = (FR + 15) / 16 * 2;            // groups per pair section
@@ -325,6 +324,11 @@ __device__ __forceinline__ void gn_apply_lds(half8 (&xf)[KS], const char* tab, i
 // tables (4 x 5 KiB behind the ring: 148 KiB of the CU's 160)
 template <int KS, bool GN>
 constexpr int lin_ring_slots() { return (GN && KS > 20) ? LinCfg<KS>::NS - 1 : LinCfg<KS>::NS; }
+// the geometry the planner (rows_plan.h) answers with is this file's
+static_assert(LIN_SLOT_FR * 1024 == ROWLIN_SLOT_BYTES, "rows_plan.h: ring slot");
+static_assert(rowlin_wgs_per_cu(20) == LinCfg<20>::WGS && rowlin_wgs_per_cu(40) == LinCfg<40>::WGS, "rows_plan.h: workgroups per CU");
+static_assert(rowlin_ring_slots(20, false) == lin_ring_slots<20, false>() && rowlin_ring_slots(20, true) == lin_ring_slots<20, true>() &&
+              rowlin_ring_slots(40, false) == lin_ring_slots<40, false>() && rowlin_ring_slots(40, true) == lin_ring_slots<40, true>(), "rows_plan.h: ring depth");
 
 template <int KS, bool LN, bool FRAME, bool RES, bool GN = false, int TB = 1>
 __global__ __launch_bounds__(256, LinCfg<KS>::WGS) void rowlin_kernel(RowLinArgs p) {
@@ -509,57 +513,53 @@ extern "C" int64_t insv2v_ffn_stream_elems(int32_t C, int32_t hidden, int32_t po
     return (int64_t)(FFN_PASS_SLOTS + (post ? FFN_POST_SLOTS : 0)) * FFN_SLOT_FR * 512;
 }
 
+// The kernel the plan names (rows_plan.h): form = LN << 2 | FRAME << 1 | RES, the GroupNorm-on-load form, one or two token blocks per wave
 template <int KS>
-static int launch_rowlin(const insv2v_rowlin_desc& d, const RowLinArgs& a, hipStream_t s) {
-    const int v = (d.layernorm ? 4 : 0) | (d.frame_bias ? 2 : 0) | (d.residual ? 1 : 0);
+static int launch_rowlin(const insv2v_rowlin_plan_t& pl, const RowLinArgs& a, hipStream_t s) {
     static const void* kernels[8] = {(const void*)rowlin_kernel<KS, false, false, false>, (const void*)rowlin_kernel<KS, false, false, true>,
                                      (const void*)rowlin_kernel<KS, false, true, false>, (const void*)rowlin_kernel<KS, false, true, true>,
                                      (const void*)rowlin_kernel<KS, true, false, false>, (const void*)rowlin_kernel<KS, true, false, true>,
                                      (const void*)rowlin_kernel<KS, true, true, false>, (const void*)rowlin_kernel<KS, true, true, true>};
     static bool attr_set[8] = {};
-    if (d.gn_ab) {   // fused input GroupNorm: only the plain form (proj_in of the transformer blocks) exists
-        if (v != 0) return INSV2V_EUNSUPPORTED;
+    const int v = pl.form;
+    if (pl.gn) {   // fused input GroupNorm: only the plain form (proj_in of the transformer blocks) exists
         static bool gn_attr = false;
-        return launch_rows((const void*)rowlin_kernel<KS, false, false, false, true>, gn_attr, lin_ring_slots<KS, true>() * LIN_SLOT_FR * 1024 + 4 * 16 * KS * 8, a, a.gn_tiles * 128, s, LinCfg<KS>::WGS);
+        return launch_grid((const void*)rowlin_kernel<KS, false, false, false, true>, gn_attr, pl.lds_bytes, a, pl.grid, s);
     }
-    if constexpr (KS == 40) {   // two token blocks per wave where the register file holds them: bit v of the mask (INSV2V_ROWLIN_TB2 overrides, for A/B)
-        static const int tb2 = getenv("INSV2V_ROWLIN_TB2") ? atoi(getenv("INSV2V_ROWLIN_TB2")) : ROWLIN_TB2_DEFAULT;
+    if constexpr (KS == 40) {   // two token blocks per wave where the register file holds them
         static const void* k2[8] = {(const void*)rowlin_kernel<KS, false, false, false, false, 2>, (const void*)rowlin_kernel<KS, false, false, true, false, 2>,
                                     (const void*)rowlin_kernel<KS, false, true, false, false, 2>, (const void*)rowlin_kernel<KS, false, true, true, false, 2>,
                                     (const void*)rowlin_kernel<KS, true, false, false, false, 2>, (const void*)rowlin_kernel<KS, true, false, true, false, 2>,
                                     (const void*)rowlin_kernel<KS, true, true, false, false, 2>, (const void*)rowlin_kernel<KS, true, true, true, false, 2>};
         static bool attr2[8] = {};
-        // only where the launch keeps >= 2 rounds of 256-row tiles (5 stacked clips at level 1 = 1.4 rounds: slower, profiles/r03_rowlin_tb2.txt)
-        if (((tb2 >> v) & 1) && (d.M + 255) / 256 >= 2 * num_cus()) return launch_rows(k2[v], attr2[v], LinCfg<KS>::NS * LIN_SLOT_FR * 1024, a, (d.M + 1) / 2, s, LinCfg<KS>::WGS);
+        if (pl.token_blocks == 2) return launch_grid(k2[v], attr2[v], pl.lds_bytes, a, pl.grid, s);
     }
-    return launch_rows(kernels[v], attr_set[v], LinCfg<KS>::NS * LIN_SLOT_FR * 1024, a, d.M, s, LinCfg<KS>::WGS);
+    if (pl.token_blocks != 1) return INSV2V_EINVAL;
+    return launch_grid(kernels[v], attr_set[v], pl.lds_bytes, a, pl.grid, s);
 }
 
-static bool rowlin_k_ok(int K) { return K == 320 || K == 640; }
+// bit v of the mask: form v runs two token blocks per wave at K = 640 (INSV2V_ROWLIN_TB2 overrides, for A/B); read once for the library
+static int rowlin_tb2_mask() {
+    static const int tb2 = getenv("INSV2V_ROWLIN_TB2") ? atoi(getenv("INSV2V_ROWLIN_TB2")) : ROWLIN_TB2_DEFAULT;
+    return tb2;
+}
+
+// ONE planner (rows_plan.h) answers for the launch and for the read-only entry, so that they cannot disagree
+extern "C" int insv2v_rowlin_plan(const insv2v_rowlin_desc* dp, int32_t cus, insv2v_rowlin_plan_t* out) {
+    if (!dp || !out) return INSV2V_EINVAL;
+    *out = plan_rowlin(*dp, rowlin_tb2_mask(), cus > 0 ? cus : insv2v_num_cus());
+    return 0;
+}
 
 extern "C" int insv2v_rowlin(const insv2v_rowlin_desc* dp, insv2v_stream_t stream) {
     if (!one_device()) return INSV2V_EINVAL;
     if (!dp) return INSV2V_EINVAL;
     const insv2v_rowlin_desc& d = *dp;
-    if (!d.x || !d.out || !d.wstream || d.M <= 0 || d.N <= 0) return INSV2V_EINVAL;
-    if (!rowlin_k_ok(d.K) || (d.N & 63)) return INSV2V_EUNSUPPORTED;
-    if (d.frame_bias && (d.rows_per_frame <= 0 || d.frames <= 0 || d.frames > 16)) return INSV2V_EUNSUPPORTED;
-    if ((d.ldx & 7) || (d.ldo & 7) || ((uintptr_t)d.x & 15) || ((uintptr_t)d.out & 15) || ((uintptr_t)d.wstream & 15)) return INSV2V_EINVAL;
-    if (d.residual && ((d.ldr & 7) || ((uintptr_t)d.residual & 15))) return INSV2V_EINVAL;
-    // (descriptors are rebased per 128/256-row tile: only a tile's own extent has to fit the 2 GiB window, the operands may be larger)
-    const int64_t lim = (int64_t)1 << 31;
-    if (256 * (int64_t)d.ldx * 2 >= lim || 256 * (int64_t)d.ldo * 2 >= lim || (d.residual && 256 * (int64_t)d.ldr * 2 >= lim)) return INSV2V_EUNSUPPORTED;
-    RowLinArgs a = {(const half_t*)d.x, (half_t*)d.out, (const half_t*)d.residual, (const half_t*)d.wstream, d.ldx, d.ldo, d.ldr,
-                    d.M, d.N, d.rows_per_frame, d.frames, d.eps, d.stats_out, d.stats_eps, d.gn_ab, d.gn_rows, 0, 0};
-    if (d.gn_ab) {
-        if (d.gn_rows <= 0 || ((uintptr_t)d.gn_ab & 15)) return INSV2V_EUNSUPPORTED;
-        // every sample (the last one may be partial) gets its own 32-row wave blocks, four of them to a tile
-        a.gn_units = (d.gn_rows + 31) / 32;
-        const int64_t blocks = ((int64_t)d.M + d.gn_rows - 1) / d.gn_rows * a.gn_units;
-        if ((blocks + 3) / 4 * 128 >= lim) return INSV2V_EUNSUPPORTED;
-        a.gn_tiles = (int)((blocks + 3) / 4);
-    }
-    return d.K == 320 ? launch_rowlin<20>(d, a, as_stream(stream)) : launch_rowlin<40>(d, a, as_stream(stream));
+    const insv2v_rowlin_plan_t pl = plan_rowlin(d, rowlin_tb2_mask(), num_cus());
+    if (pl.rc) return pl.rc;
+    const RowLinArgs a = {(const half_t*)d.x, (half_t*)d.out, (const half_t*)d.residual, (const half_t*)d.wstream, d.ldx, d.ldo, d.ldr,
+                          d.M, d.N, d.rows_per_frame, d.frames, d.eps, d.stats_out, d.stats_eps, d.gn_ab, d.gn_rows, pl.gn_units, pl.gn ? pl.ntiles : 0};
+    return pl.ks == 20 ? launch_rowlin<20>(pl, a, as_stream(stream)) : launch_rowlin<40>(pl, a, as_stream(stream));
 }
 
 // fp16 elements of the weight stream insv2v_rowlin expects for a [N, K] Linear; 0 if unsupported

@@ -60,6 +60,11 @@ class RowLinDesc(C.Structure):
                 ("frames", c_i32), ("eps", c_f32), ("stats_out", c_p), ("stats_eps", c_f32), ("gn_ab", c_p), ("gn_rows", c_i32)]
 
 
+class RowLinPlan(C.Structure):
+    """insv2v_rowlin_plan_t: what insv2v_rowlin does with a descriptor (insv2v_rowlin_plan; csrc/rows_plan.h)."""
+    _fields_ = [(n, c_i32) for n in ("rc", "ks", "form", "gn", "token_blocks", "tile_rows", "ntiles", "grid", "rounds", "wgs_per_cu", "lds_bytes", "gn_units")]
+
+
 class TattnDesc(C.Structure):
     _fields_ = [("x", c_p), ("out", c_p), ("wstream", c_p), ("ldx", c_i64), ("ldo", c_i64),
                 ("samples", c_i32), ("HW", c_i32), ("C", c_i32), ("heads", c_i32), ("frames", c_i32), ("eps", c_f32), ("scale", c_f32)]
@@ -208,6 +213,7 @@ SIGNATURES = {
     "insv2v_ffn_stream_elems": (c_i64, [c_i32, c_i32, c_i32]),
     "insv2v_rowlin": (c_i32, [C.POINTER(RowLinDesc), c_p]),
     "insv2v_rowlin_stream_elems": (c_i64, [c_i32, c_i32]),
+    "insv2v_rowlin_plan": (c_i32, [C.POINTER(RowLinDesc), c_i32, C.POINTER(RowLinPlan)]),
     "insv2v_tattn_fused": (c_i32, [C.POINTER(TattnDesc), c_p]),
     "insv2v_tattn_stream_elems": (c_i64, [c_i32, c_i32, c_i32]),
     "insv2v_tattn_attn": (c_i32, [C.POINTER(TattnDesc), c_p]),

@@ -256,6 +256,26 @@ def rowlin(x, wstream, N, *, layernorm=False, residual=None, frames=0, rows_per_
     return (out, stats) if emit_stats else out
 
 
+def rowlin_plan(M, N, K, *, layernorm=False, residual=False, frames=0, rows_per_frame=0, gn_rows=0, cus=0, **over):
+    """What insv2v_rowlin does with this problem (insv2v_rowlin_plan, csrc/rows_plan.h): the filled _lib.RowLinPlan - kernel form, one or
+    two token blocks per wave, tiles, grid and rounds, or its refusal in .rc.  The descriptor is contiguous with placeholder aligned
+    pointers (the planner looks at null and alignment bits only); gn_rows > 0: the GroupNorm-on-load form; cus = 0: this device's CU
+    count; `over` sets further descriptor fields (strides, pointers) for the planner's refusals.  Touches no GPU."""
+    lib = _lib.load()
+    d, p = RowLinDesc(), _lib.RowLinPlan()
+    d.x, d.out, d.wstream, d.ldx, d.ldo = 4096, 8192, 12288, K, N
+    if residual:   # (True, or a placeholder address of its own)
+        d.residual, d.ldr = 16384 if residual is True else int(residual), N
+    d.M, d.N, d.K, d.layernorm, d.eps = M, N, K, int(layernorm), 1e-5
+    d.frame_bias, d.rows_per_frame, d.frames = int(frames > 0), rows_per_frame, frames
+    if gn_rows > 0:
+        d.gn_ab, d.gn_rows = 20480, gn_rows
+    for key, val in over.items():
+        setattr(d, key, val)
+    check(lib.insv2v_rowlin_plan(_byref(d), cus, _byref(p)), "insv2v_rowlin_plan")
+    return p
+
+
 def tattn_fused_supported(C, heads, frames):
     """True if insv2v_tattn_fused handles this temporal attention block (C = 320, 8 heads, a window of 1 .. 32 frames)."""
     return int(_lib.load().insv2v_tattn_stream_elems(C, heads, frames)) > 0
