@@ -1066,6 +1066,64 @@ typedef struct insv2v_temporal_filter_desc {
 int insv2v_temporal_filter(const insv2v_temporal_filter_desc* d, insv2v_stream_t stream);
 
 /*
+ * ---- filling the frames between edited key frames (an addition to ABI 15: no existing struct or entry changes) ---------------------------
+ * Only every N-th frame of a video is denoised; the frames in between take the edit from their neighbouring key frames along the SOURCE
+ * video's motion (csrc/keyfill.hip; tests/keyfill_ref.py restates the definition in float64).
+ * A [T,3,H,W] is the source video: its raw values x are used for the residual and the result, a = clamp(x * scale + shift, 0, 1) for
+ * the photometric weight, exactly as insv2v_temporal_filter reads its guide.  E [Tk,3,H,W] holds the edited key frames (scale / shift
+ * are not read); key slot j is frame key_frame[j] of A.  Entry i of the frame table is the in-between frame t = frame[i] with up to two
+ * sides, s = 0 (the previous key) and s = 1 (the next key): slot[i][s] is the side's key slot (-1: the side does not exist),
+ * weight[i][s] = tw_s >= 0 its temporal weight (tw_0 + tw_1 = 1 over the existing sides), G_s = flow[i][s] is defined on frame t and
+ * points into the key's frame (the convention of insv2v_warp_image) and U_s = valid[i][s] is 1 where that trajectory may be followed.
+ * A side is ACTIVE at pixel x when its slot is >= 0 and U_s(x) > 1/2.  An inactive side's G, and the taps it would reach, are not
+ * read: a NaN there cannot leak.  Per active side, in the order s = 0, 1, with p = x + G_s(x), its clamp and the sample S(.) exactly
+ * as defined for insv2v_mask_track_step (mt_taps / mt_lerp of csrc/flow_sample.h):
+ *   d2_s   = (1/3) sum_c (a_t[c](x) - S(a_key[c]))^2          fp32: the three squares added in channel order, then divided by 3
+ *   w_s    = tw_s * expf(d2_s * (-1 / (2 sigma^2)))           the factor is formed in double on the host and rounded once
+ *   r_s[c] = S(E_key[c] - A_key[c])                           mode INSV2V_KEYFILL_RESIDUAL: the lerp over the four per-tap differences,
+ *                                                             each formed in fp32 with A raw - exactly 0 when E == A in all four taps
+ *   r_s[c] = S(E_key[c]) - A_t[c](x)                          mode INSV2V_KEYFILL_WARP
+ * With Wsum = sum of w_s over the active sides:
+ *   Wsum > 0:   out[c] = A_t[c](x) + (sum_s w_s r_s[c]) / Wsum,  conf(x) = Wsum (in (0, 1])
+ *   otherwise (a hole: no active side, or every weight underflowed):
+ *               out[c] = A_t[c](x) + sum over the sides with slot >= 0 of tw'_s r0_s[c],  conf(x) = 0
+ *               r0_s = the same quantity taken at x itself, no flow read; tw' = tw renormalised over the existing sides (formed in
+ *               double on the host, rounded once)
+ * and out = A_t[c](x) itself, converted once to the output dtype, when the added term q is 0 (q == 0.f): where the edit changed
+ * nothing in the taps of its keys the in-between pixel is the source's - bit for bit when A and the output share a dtype.
+ * All arithmetic is fp32; the output has E's dtype and is rounded once, on the store.  `out` is the FULL-RATE tensor [T,3,H,W]: only
+ * the frames of the table are written, the key frames' rows are not touched.  conf [n,H,W] fp32 may be NULL.  One thread writes one
+ * pixel: no atomics, two calls give the same bits.  Nothing is allocated, nothing is copied to the device and nothing synchronises (the
+ * tables are HOST arrays, validated here and passed to the kernel by value in launches of at most INSV2V_KEYFILL_MAX_FRAMES frames),
+ * so the call can be captured.
+ * INSV2V_EINVAL, nothing launched and no output touched: a NULL descriptor or required pointer; n < 1, Tk < 1 or T < 1; H <= 1 or
+ * W <= 1; a frame or key_frame[j] outside 0 .. T-1; a frame listed twice or equal to a key frame; a slot outside -1 .. Tk-1; both
+ * slots -1; a weight that is negative or not finite, or whose existing sides do not sum to 1 within 1e-6; sigma not finite or <= 0
+ * (or 2 sigma^2 underflowing); a mode other than 0 / 1; a guide affine that is not finite; a negative stride or a row stride below W;
+ * T or Tk above 65535 or a plane beyond the grid (the limits of insv2v_temporal_filter); an output or conf that overlaps any input or
+ * each other.
+ */
+#define INSV2V_KEYFILL_MAX_FRAMES 64
+#define INSV2V_KEYFILL_RESIDUAL 0
+#define INSV2V_KEYFILL_WARP 1
+typedef struct insv2v_keyfill_desc {
+    insv2v_frames_view a;      /* the source video [T,3,H,W] */
+    insv2v_frames_view e;      /* the edited key frames [Tk,3,H,W]; scale / shift are not read */
+    const float* flow;         /* [n,2,2,H,W] contiguous: frame, side, (x, y) */
+    const float* valid;        /* [n,2,H,W] contiguous, 0 or 1 */
+    void* out;                 /* [T,3,H,W] of E's dtype, element strides below, x contiguous */
+    int64_t out_stride_t, out_stride_c, out_stride_h;
+    float* conf;               /* [n,H,W] contiguous, or NULL */
+    const int32_t* key_frame;  /* HOST [Tk] */
+    const int32_t* frame;      /* HOST [n] */
+    const int32_t* slot;       /* HOST [n,2] */
+    const float* weight;       /* HOST [n,2] */
+    int32_t n, T, Tk, H, W, mode;
+    float sigma;
+} insv2v_keyfill_desc;
+int insv2v_keyframe_fill(const insv2v_keyfill_desc* d, insv2v_stream_t stream);
+
+/*
  * ---- growing, shrinking and feathering a mask (an addition to ABI 15: no existing struct or entry changes) --------------------------------
  * A mask m [T,H,W] fp32 from any source becomes the two masks a localized edit wants (csrc/mask_shape.hip, DESIGN.md section 22;
  * tests/mask_shape_ref.py restates the definition with integers and float64): `shaped`, soft, for the pixel composite, and `support`,

@@ -15,7 +15,7 @@ def __getattr__(name):
         "InferenceIP2PVideoOpticalFlow": ".inference", "Inference": ".inference",
         "InstructP2PVideoModel": ".model", "create_model": ".model", "unit_test_create_model": ".model",
         "warp_image": ".flow_utils", "resize_flow": ".flow_utils", "split_batch": ".run_loveu_tgve",
-        "edit_video": ".run_loveu_tgve",
+        "edit_video": ".run_loveu_tgve", "keyframe_fill": ".keyfill", "key_frames": ".keyfill",
     }
     if name in table:
         return getattr(importlib.import_module(table[name], __name__), name)

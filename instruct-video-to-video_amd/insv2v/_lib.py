@@ -184,6 +184,17 @@ class TemporalFilterDesc(C.Structure):
                 ("K", c_i32), ("T", c_i32), ("H", c_i32), ("W", c_i32), ("sigma", c_f32), ("strength", c_f32)]
 
 
+KEYFILL_MAX_FRAMES, KEYFILL_MODES = 64, ("residual", "warp")   # INSV2V_KEYFILL_MAX_FRAMES, INSV2V_KEYFILL_RESIDUAL / _WARP in their order
+
+
+class KeyfillDesc(C.Structure):
+    """insv2v_keyfill_desc (csrc/keyfill.hip); key_frame, frame, slot and weight are HOST arrays."""
+    _fields_ = [("a", FramesView), ("e", FramesView), ("flow", c_p), ("valid", c_p), ("out", c_p),
+                ("out_stride_t", c_i64), ("out_stride_c", c_i64), ("out_stride_h", c_i64), ("conf", c_p),
+                ("key_frame", C.POINTER(c_i32)), ("frame", C.POINTER(c_i32)), ("slot", C.POINTER(c_i32)), ("weight", C.POINTER(c_f32)),
+                ("n", c_i32), ("T", c_i32), ("Tk", c_i32), ("H", c_i32), ("W", c_i32), ("mode", c_i32), ("sigma", c_f32)]
+
+
 MASK_SHAPE_MAX, MASK_PROFILES = 32, ("linear", "smooth")   # INSV2V_MASK_SHAPE_MAX, INSV2V_MASK_PROFILE_* in their order
 
 
@@ -271,6 +282,7 @@ SIGNATURES = {
     "insv2v_frame_fidelity": (c_i32, [C.POINTER(FidelityDesc), c_p]),
     "insv2v_frame_fidelity_tile": (c_i32, [C.POINTER(c_i32), C.POINTER(c_i32)]),
     "insv2v_temporal_filter": (c_i32, [C.POINTER(TemporalFilterDesc), c_p]),
+    "insv2v_keyframe_fill": (c_i32, [C.POINTER(KeyfillDesc), c_p]),
     "insv2v_mask_shape_plan": (c_i32, [c_f32, c_f32, C.POINTER(MaskShapePlan)]),
     "insv2v_mask_shape_workspace_bytes": (c_i64, [c_i32, c_i32, c_i32]),
     "insv2v_mask_shape": (c_i32, [C.POINTER(MaskShapeDesc), c_p]),

@@ -1355,6 +1355,50 @@ def temporal_filter(edited, guide, flow, valid, offsets, *, sigma=0.1, strength=
     return out
 
 
+# ----------------------------------------------------------------------------- filling between key frames (insv2v/keyfill.py)
+def keyframe_fill(source, edited_keys, flow, valid, key_frame, frames, slots, weights, *, sigma=0.1, mode="residual", guide_affine=(1.0, 0.0),
+                  out=None, conf=None):
+    """insv2v_keyframe_fill (tests/keyfill_ref.py is the definition): ``source`` [T,3,H,W] and ``edited_keys``
+    [Tk,3,H,W], each fp16 or fp32 and any view with contiguous rows (the source is read raw for the residual and as ``clamp(x * scale +
+    shift, 0, 1)`` for the photometric weight), ``flow`` [n,2,2,H,W] and ``valid`` [n,2,H,W] fp32 contiguous; the host tables
+    ``key_frame`` (Tk frame indices), ``frames`` (n in-between frames), ``slots`` (n pairs of key slots, -1 = no such side) and
+    ``weights`` (n pairs of temporal weights) -> (out, conf): ``out`` the FULL-RATE [T,3,H,W] in ``edited_keys``' dtype, of which only
+    the rows of ``frames`` are written (preallocated: any view with contiguous rows, its other rows are not touched; default: a new
+    tensor whose other rows are uninitialised), ``conf`` [n,H,W] fp32 (preallocated, or ``False``: not computed)."""
+    lib = _lib.load()
+    d = _lib.KeyfillDesc()
+    T, _, H, W = _frames_view(d.a, source, "keyframe_fill.source", *guide_affine)
+    Tk = _frames_view(d.e, edited_keys, "keyframe_fill.edited_keys", 1.0, 0.0)[0]
+    if tuple(edited_keys.shape[1:]) != (3, H, W):
+        raise _lib.HipKernelError(f"keyframe_fill: source {tuple(source.shape)} and edited_keys {tuple(edited_keys.shape)} differ in frame size")
+    if mode not in _lib.KEYFILL_MODES:
+        raise ValueError(f"keyframe_fill: mode {mode!r} is neither 'residual' nor 'warp'")
+    key_frame, frames = [int(k) for k in key_frame], [int(t) for t in frames]
+    slots, weights = [[int(v) for v in s] for s in slots], [[float(v) for v in w] for w in weights]
+    n = len(frames)
+    if len(key_frame) != Tk or len(slots) != n or len(weights) != n or any(len(s) != 2 for s in slots) or any(len(w) != 2 for w in weights):
+        raise _lib.HipKernelError(f"keyframe_fill: {len(key_frame)} key frames for {Tk} slots, {len(slots)} slot pairs and {len(weights)} weight pairs for {n} frames")
+    _plain(flow, (n, 2, 2, H, W), "keyframe_fill.flow")
+    _plain(valid, (n, 2, H, W), "keyframe_fill.valid")
+    if out is None:
+        out = torch.empty((T, 3, H, W), device=edited_keys.device, dtype=edited_keys.dtype)
+    ov = _lib.FramesView()
+    if _frames_view(ov, out, "keyframe_fill.out", 1.0, 0.0) != (T, 3, H, W) or out.dtype != edited_keys.dtype:
+        raise _lib.HipKernelError(f"keyframe_fill: out {tuple(out.shape)} {out.dtype} must be {(T, 3, H, W)} {edited_keys.dtype}")
+    if conf is None:
+        conf = torch.empty((n, H, W), device=edited_keys.device, dtype=torch.float32)
+    if conf is not False:
+        _plain(conf, (n, H, W), "keyframe_fill.conf")
+    d.flow, d.valid, d.out, d.conf = flow.data_ptr() or None, valid.data_ptr() or None, ov.p, None if conf is False else (conf.data_ptr() or None)
+    d.out_stride_t, d.out_stride_c, d.out_stride_h = ov.stride_t, ov.stride_c, ov.stride_h
+    tables = ((C.c_int32 * max(Tk, 1))(*key_frame), (C.c_int32 * max(n, 1))(*frames), (C.c_int32 * max(2 * n, 1))(*[v for s in slots for v in s]),
+              (C.c_float * max(2 * n, 1))(*[v for w in weights for v in w]))   # host arrays: the entry reads them before it returns
+    d.key_frame, d.frame, d.slot, d.weight = tables
+    d.n, d.T, d.Tk, d.H, d.W, d.mode, d.sigma = n, T, Tk, H, W, _lib.KEYFILL_MODES.index(mode), sigma
+    check(lib.insv2v_keyframe_fill(_byref(d), _stream()), "insv2v_keyframe_fill")
+    return out, (None if conf is False else conf)
+
+
 # ----------------------------------------------------------------------------- shaping a mask (insv2v/mask_shape.py)
 def mask_shape_plan(grow, feather):
     """insv2v_mask_shape_plan: the search radius, FAR and the four integer thresholds of (grow, feather) as a dict; launches nothing."""

@@ -22,6 +22,9 @@ DESIGN.md section 22): the composite gets the soft mask, the latent hold the har
 
 ``stabilize=`` / ``--stabilize`` filters a unit's decoded frames along the SOURCE video's optical flow, once per unit and after its last
 window (``insv2v/temporal_filter.py``): the switch to pull when ``--score-warp`` shows flicker.
+
+``keyframes=`` / ``--key-stride`` denoises only every N-th frame of a unit and fills the frames in between along the SOURCE video's
+optical flow (``insv2v/keyfill.py``): about N times the delivered frames per GPU second.
 """
 import argparse
 import os
@@ -68,8 +71,11 @@ MASK_TRACK_KEYS = ("occlusion", "alpha", "beta", "fill")
 STABILIZE_KEYS = ("radius", "sigma", "strength", "occlusion", "alpha", "beta")
 
 
+KEYFRAME_KEYS = ("stride", "mode", "sigma", "occlusion", "alpha", "beta")
+
+
 def check_edit_args(frames_shape, mask=None, strength=1.0, mask_mode="max", auto_mask=None, mask_key=None, mask_flows=None, mask_track=None,
-                    stabilize=None, stabilize_flows=None, mask_shape=None):
+                    stabilize=None, stabilize_flows=None, mask_shape=None, keyframes=None, key_flows=None):
     """Host-side check of the localized / partial edit controls (nothing is launched): ``strength`` in (0, 1], ``mask_mode`` "mean" or
     "max", ``mask`` a floating-point [1,T,H,W] or [1,1,H,W] tensor for frames [1,T,3,H,W] with H and W multiples of 8 - or the string
     "auto" (the mask is estimated from the prompt, ``InferenceIP2PVideo.estimate_mask``), then optionally with ``auto_mask``, a dict of
@@ -78,8 +84,11 @@ def check_edit_args(frames_shape, mask=None, strength=1.0, mask_mode="max", auto
     ``mask_track``, a dict of ``propagate_mask``'s keywords (``MASK_TRACK_KEYS``).  ``stabilize`` (None, True or a dict of
     ``temporal_filter.stabilize``'s parameters, ``STABILIZE_KEYS``) optionally with ``stabilize_flows``, a dict(fwd=, bwd=) of the source
     video's [T-1,2,H,W] flows.  ``mask_shape`` (None or a dict of ``mask_shape.check_shape_args``' parameters, ``MASK_SHAPE_KEYS``) shapes
-    the mask of any source, so it needs one."""
+    the mask of any source, so it needs one.  ``keyframes`` (None, an int stride or a dict with keys among ``KEYFRAME_KEYS``) optionally
+    with ``key_flows``, a dict(fwd=, bwd=) of the source video's [T-1,2,H,W] flows; not together with ``mask="auto"`` (an estimated mask
+    exists on the key frames only)."""
     strength_to_start(strength, 1)
+    _check_keyframe_args(frames_shape, mask, keyframes, key_flows)
     if mask_shape is not None:
         from .mask_shape import check_mask_shape
         check_mask_shape(mask_shape)
@@ -176,6 +185,109 @@ def _check_stabilize_args(frames_shape, stabilize, stabilize_flows):
         for k, f in stabilize_flows.items():
             if f is not None and (not torch.is_tensor(f) or not f.is_floating_point() or tuple(f.shape) != (T - 1, 2, H, W)):
                 raise ValueError(f"stabilize_flows[{k!r}] {tuple(getattr(f, 'shape', ()))} must be a floating-point [{T - 1},2,{H},{W}] for frames {tuple(frames_shape)}")
+
+
+def _keyframe_params(keyframes):
+    """None when every frame is denoised, else the dict of the key-frame edit's parameters (an int: its stride)."""
+    if keyframes is None or keyframes is False:
+        return None
+    return dict(stride=keyframes) if isinstance(keyframes, int) and not isinstance(keyframes, bool) else keyframes
+
+
+def _check_keyframe_args(frames_shape, mask, keyframes, key_flows):
+    """The ``keyframes`` part of ``check_edit_args``."""
+    from .keyfill import check_fill_args
+    params = _keyframe_params(keyframes)
+    if params is None:
+        if key_flows is not None:
+            raise ValueError("key_flows belongs to a key-frame edit: pass keyframes= (a stride, or a dict of its parameters) with it")
+        return
+    if not isinstance(params, dict) or set(params) - set(KEYFRAME_KEYS):
+        raise ValueError(f"keyframes must be None, an int stride or a dict with keys among {KEYFRAME_KEYS}, got {keyframes!r}")
+    try:
+        check_fill_args(**params)
+    except ValueError as e:
+        raise ValueError(f"keyframes (the parameters of the key-frame edit): {e}") from None
+    b, T, _, H, W = frames_shape
+    if b != 1:
+        raise ValueError(f"keyframes needs frames [1,T,3,H,W], not {tuple(frames_shape)}")
+    if isinstance(mask, str):
+        raise ValueError("keyframes and mask=\"auto\": an estimated mask exists on the key frames only (carrying it to the frames in between "
+                         "is not built); draw the mask, or track one with mask_key=")
+    if key_flows is not None:
+        if not isinstance(key_flows, dict) or set(key_flows) - {"fwd", "bwd"} or key_flows.get("fwd") is None or key_flows.get("bwd") is None:
+            raise ValueError(f"key_flows must be a dict(fwd=, bwd=) of the source video's [{T - 1},2,{H},{W}] flows (the previous key is reached along bwd, the next along fwd)")
+        for k, f in key_flows.items():
+            if not torch.is_tensor(f) or not f.is_floating_point() or tuple(f.shape) != (T - 1, 2, H, W):
+                raise ValueError(f"key_flows[{k!r}] {tuple(getattr(f, 'shape', ()))} must be a floating-point [{T - 1},2,{H},{W}] for frames {tuple(frames_shape)}")
+
+
+_FULL_RATE_ONLY = ("keyframes", "key_flows", "mask_key", "mask_flows", "mask_track", "stabilize", "stabilize_flows")
+
+
+def _keyframe_prepare(inf_pipe, frames, kf, u, flow_estimator, dev):
+    """``keyframes=``: what a unit needs before the first window of its key frames -> None when every frame is a key (the unit is then
+    edited as if ``keyframes`` were not given), else (changed, state): ``changed`` holds the arguments of ``edit_video`` that the
+    sub-video of the key frames takes in place of the unit's (``frames``, ``cond``, ``enc_noise``, ``mask``; the arguments of
+    ``_FULL_RATE_ONLY`` are dropped), ``state`` what ``_keyframe_finish`` needs.  ``u``: the unit's arguments by name.  The source video's
+    flows - ``key_flows``, ``stabilize_flows``, ``mask_flows`` (each when it holds both sets), ``flow_estimator``, the pipe's own
+    estimator, in this order - are computed at most once, at full rate, and serve the fill, a tracked mask and the filter; a ``mask_key``
+    mask is tracked over the FULL-RATE video."""
+    from .keyfill import key_frames, FILL_DEFAULTS
+    from .mask_track import pair_flows
+    T = frames.shape[1]
+    keys = key_frames(T, kf.get("stride", FILL_DEFAULTS["stride"]))
+    if len(keys) == T:
+        return None
+    both = lambda f: f is not None and f.get("fwd") is not None and f.get("bwd") is not None   # noqa: E731
+    flows = next((f for f in (u.get("key_flows"), u.get("stabilize_flows"), u.get("mask_flows")) if both(f)), None)
+    if flows is None:
+        est = flow_estimator if flow_estimator is not None else getattr(inf_pipe, "flow_estimator", None)
+        if est is None:
+            raise RuntimeError("key-frame edit (keyframes=) without a flow source: pass key_flows=, stabilize_flows=, mask_flows= or flow_estimator=, or build the pipe with flow_estimator=")
+        flows = pair_flows(frames, est, both=True)
+    mask, est, shape = u.get("mask"), None, None
+    if u.get("mask_key") is not None:
+        est = _track_mask(inf_pipe, frames, mask, u["mask_key"], u["mask_flows"] if u.get("mask_flows") is not None else flows, flow_estimator,
+                          u.get("mask_track"), dev)
+        mask = est["mask"]
+    mask_img = None
+    if mask is not None:   # the full-rate mask of the composite, shaped per frame exactly as the sub-video's plan shapes its rows
+        mask_img = mask.to(device=dev, dtype=torch.float32).expand(1, T, *mask.shape[2:])[0].contiguous()
+        if u.get("mask_shape") is not None:
+            from .mask_shape import shape_mask
+            mask_img, support = shape_mask(mask_img, **u["mask_shape"])
+            shape = dict(shaped=mask_img[None], support=support[None])
+    changed = dict(frames=frames[:, keys])
+    for k in ("cond", "enc_noise"):
+        if u.get(k) is not None:
+            changed[k] = u[k][:, keys]
+    if mask is not None:
+        changed["mask"] = mask if mask.shape[1] == 1 else mask[:, keys]
+    stab = _stabilize_params(u.get("stabilize"))
+    state = dict(kf=kf, keys=keys, flows=flows, mask_img=mask_img, est=est if shape is None else dict(est or {}, **shape), stab=stab,
+                 sflows=u["stabilize_flows"] if u.get("stabilize_flows") is not None else flows)
+    return changed, state
+
+
+def _keyframe_finish(state, frames, key_image, dev):
+    """The edited key frames [1,Tk,3,H,W] of a unit -> (its full-rate result [1,T,3,H,W], the ``return_mask`` dict): the frames in
+    between are filled along the source's flow (``keyfill.keyframe_fill``), with a mask each of them is composited against the input
+    with its own mask exactly as the key frames were (``ops.composite``), and ``stabilize`` runs once, on the full-rate result.  The key
+    frames stay ``key_image``'s bit for bit unless the filter runs."""
+    from .keyfill import keyframe_fill
+    kf, keys = state["kf"], state["keys"]
+    fill = keyframe_fill(frames, key_image, keys, flows=state["flows"], **{k: kf[k] for k in ("mode", "sigma", "occlusion", "alpha", "beta") if k in kf})
+    image = fill["frames"]
+    if state["mask_img"] is not None:
+        rows = torch.tensor([t for t in range(frames.shape[1]) if t not in keys], dtype=torch.long, device=image.device)
+        img = image[0].index_select(0, rows).to(torch.float32).contiguous()
+        orig = frames[0].to(device=img.device, dtype=torch.float32).index_select(0, rows).contiguous()
+        img = ops.composite(img, orig, state["mask_img"].index_select(0, rows).contiguous(), out=img)
+        image[0].index_copy_(0, rows, img.to(image.dtype))
+    if state["stab"] is not None:
+        image = _stabilize(frames, image, state["stab"], state["sflows"], state["mask_img"])
+    return image, dict(state["est"] or {}, keys=list(keys), confidence=fill["confidence"])
 
 
 def _start_time(inf_pipe, strength):
@@ -304,7 +416,8 @@ def _result(image, latent, est, return_latent, return_mask):
 def edit_video(model, inf_pipe, frames, text_cond, text_uncond, text_cfg=7.5, video_cfg=1.8, frames_in_batch=16,
                num_ref_frames=4, init_noises=None, enc_noise=None, flows_per_window=None, return_latent=False, cond=None,
                seed=None, unit=0, mask=None, strength=1.0, mask_mode="max", auto_mask=None, return_mask=False,
-               mask_key=None, mask_flows=None, flow_estimator=None, mask_track=None, stabilize=None, stabilize_flows=None, mask_shape=None):
+               mask_key=None, mask_flows=None, flow_estimator=None, mask_track=None, stabilize=None, stabilize_flows=None, mask_shape=None,
+               keyframes=None, key_flows=None):
     """frames [1,T,3,H,W] in [-1,1] -> edited frames [1,T,3,H,W] clipped to [-1,1].
 
     ``seed`` (default None: every draw comes from the global torch generators, as before) makes the edit reproducible: the posterior
@@ -353,10 +466,37 @@ def edit_video(model, inf_pipe, frames, text_cond, text_uncond, text_cfg=7.5, vi
     uses ``shaped``, the mask grown by ``grow`` and feathered over ``feather`` pixels outside the grown edge; the latent hold uses
     ``support``, the hard region ``shaped > 0``, reduced with "max" - so ``mask_mode`` has no effect when ``mask_shape`` is given.  Outside
     ``support`` the pixels are the input's bit for bit.  ``return_mask=True`` then returns a dict that also holds ``shaped`` and
-    ``support`` [1,T,H,W] (for a drawn mask: only those).  Without ``mask_shape`` nothing of this runs."""
-    check_edit_args(frames.shape, mask, strength, mask_mode, auto_mask, mask_key, mask_flows, mask_track, stabilize, stabilize_flows, mask_shape)
+    ``support`` [1,T,H,W] (for a drawn mask: only those).  Without ``mask_shape`` nothing of this runs.
+
+    ``keyframes`` (an int stride in 2 .. 8, or a dict with keys among ``KEYFRAME_KEYS``): only the key frames
+    ``keyfill.key_frames(T, stride)`` - 0, stride, 2 stride, ... and always T - 1 - are denoised, and the frames in between take the edit
+    from their two neighbouring keys along the SOURCE video's optical flow (``keyfill.keyframe_fill``).  The edit of the key frames is
+    exactly ``edit_video(frames[:, keys], ...)`` with the same seed and unit id (``cond`` / ``enc_noise`` are indexed with the keys;
+    ``init_noises`` / ``flows_per_window`` belong to that sub-video), so the key frames of the result are that call's, bit for bit.  The
+    flows are ``key_flows`` (dict(fwd=, bwd=) of [T-1,2,H,W]), else ``stabilize_flows``, else ``mask_flows``, else computed by
+    ``flow_estimator`` (default: the pipe's own) - ONE full-rate ``pair_flows(both=True)`` per unit, which also serves ``mask_key`` and
+    ``stabilize``.  A ``mask_key`` mask is tracked over the full-rate video; with a mask every in-between frame is composited against
+    the input with its own mask (``mask_shape``: shaped at full rate), so outside it every delivered frame is the input's, bit for bit;
+    ``stabilize`` runs once, on the full-rate result.  ``return_latent`` returns the key frames' latent; ``return_mask`` a dict that also
+    holds ``keys`` and ``confidence`` [T,H,W] (1 on the key frames).  Not with ``mask="auto"``.  Untuned starting values, as the filter's.
+    Without ``keyframes`` nothing of this runs."""
+    check_edit_args(frames.shape, mask, strength, mask_mode, auto_mask, mask_key, mask_flows, mask_track, stabilize, stabilize_flows, mask_shape,
+                    keyframes, key_flows)
     dev = model.unet.device
     est = None
+    kf = _keyframe_params(keyframes)
+    if kf is not None:   # before the first window: a missing flow source raises before anything is sampled
+        named = dict(mask=mask, mask_key=mask_key, mask_flows=mask_flows, mask_track=mask_track, stabilize=stabilize, stabilize_flows=stabilize_flows,
+                     mask_shape=mask_shape, key_flows=key_flows, cond=cond, enc_noise=enc_noise)
+        prep = _keyframe_prepare(inf_pipe, frames, kf, named, flow_estimator, dev)
+        if prep is not None:
+            changed, state = prep
+            sub = dict(dict(cond=cond, enc_noise=enc_noise, mask=mask), **changed)
+            image, latent = edit_video(model, inf_pipe, sub.pop("frames"), text_cond, text_uncond, text_cfg, video_cfg, frames_in_batch, num_ref_frames,
+                                       init_noises=init_noises, flows_per_window=flows_per_window, return_latent=True, seed=seed, unit=unit,
+                                       strength=strength, mask_mode=mask_mode, mask_shape=mask_shape, **sub)
+            image, est = _keyframe_finish(state, frames, image, dev)
+            return _result(image, latent, est, return_latent, return_mask)
     stab, sflows = _stabilize_params(stabilize), None
     if stab is not None:   # before the first window: a missing flow source raises before anything is sampled
         sflows, computed = _stabilize_flows(inf_pipe, frames, stab, stabilize_flows, mask_flows, flow_estimator)
@@ -439,20 +579,23 @@ def edit_videos(model, inf_pipe, units, frames_in_batch=16, num_ref_frames=4, re
     the units without ``mask_flows`` (default: the pipe's own).  Tracked, drawn, auto and unmasked units stack together.  A unit may carry
     ``stabilize`` (and ``stabilize_flows``) as for ``edit_video``: it is filtered alone, after the stacked windows have finished, bit for
     bit as ``edit_video`` filters it; stabilized and plain units stack together.  A unit may carry ``mask_shape`` as for ``edit_video``: its
-    mask is shaped alone, before the stacked windows start, bit for bit as ``edit_video`` shapes it."""
+    mask is shaped alone, before the stacked windows start, bit for bit as ``edit_video`` shapes it.  A unit may carry ``keyframes`` (and
+    ``key_flows``) as for ``edit_video``: the units' SUB-VIDEOS of key frames are what stack - they must share a shape, under the same
+    ValueError - and each unit is filled alone, after the stacked windows, bit for bit as ``edit_video`` fills it; its latent is its key
+    frames'."""
     if len(units) == 0:
         return []
     for u in units:
         check_edit_args(u["frames"].shape, u.get("mask"), u.get("strength", 1.0), u.get("mask_mode", "max"), u.get("auto_mask"),
                         u.get("mask_key"), u.get("mask_flows"), u.get("mask_track"), u.get("stabilize"), u.get("stabilize_flows"),
-                        u.get("mask_shape"))
+                        u.get("mask_shape"), u.get("keyframes"), u.get("key_flows"))
     if len({_start_time(inf_pipe, u.get("strength", 1.0)) for u in units}) > 1:
         raise ValueError("edit_videos: the units of one call must share the number of executed steps (strength); edit the others separately")
     wants_flow = hasattr(inf_pipe, "obtain_flow_batched")
     ids = [u.get("unit", j) for j, u in enumerate(units)]
     if len(units) == 1:
         keys = ("text_cfg", "video_cfg", "init_noises", "enc_noise", "cond", "flows_per_window", "mask", "strength", "mask_mode", "auto_mask",
-                "mask_key", "mask_flows", "mask_track", "stabilize", "stabilize_flows", "mask_shape")
+                "mask_key", "mask_flows", "mask_track", "stabilize", "stabilize_flows", "mask_shape", "keyframes", "key_flows")
         more = {"return_mask": True} if return_mask else {}   # (a plain call carries no new keyword)
         if flow_estimator is not None:
             more["flow_estimator"] = flow_estimator
@@ -460,7 +603,26 @@ def edit_videos(model, inf_pipe, units, frames_in_batch=16, num_ref_frames=4, re
                            num_ref_frames=num_ref_frames, return_latent=return_latent, seed=seed, unit=ids[0], **more,
                            **{k: u[k] for k in keys if k in u}) for u in units]
     dev = model.unet.device
-    cap = {} if max_clips is None else {"max_clips": max_clips}   # (a pipe without the parameter keeps working with the default)
+    if any(_keyframe_params(u.get("keyframes")) is not None for u in units):
+        # key-frame units: each is prepared alone (its flows, its tracked mask), the SUB-VIDEOS of all units stack, each is filled alone
+        subs, states = [], []
+        for u, uid in zip(units, ids):
+            kf = _keyframe_params(u.get("keyframes"))
+            prep = None if kf is None else _keyframe_prepare(inf_pipe, u["frames"], kf, u, flow_estimator, dev)
+            if prep is None:
+                subs.append(dict({k: v for k, v in u.items() if k not in ("keyframes", "key_flows")}, unit=uid))
+            else:
+                subs.append(dict({k: v for k, v in u.items() if k not in _FULL_RATE_ONLY}, unit=uid, **prep[0]))
+            states.append(None if prep is None else prep[1])
+        got = edit_videos(model, inf_pipe, subs, frames_in_batch, num_ref_frames, return_latent=True, seed=seed, max_clips=max_clips,
+                          return_mask=True, flow_estimator=flow_estimator)
+        outs = []
+        for u, state, (image, latent, est) in zip(units, states, got):
+            if state is not None:
+                image, est = _keyframe_finish(state, u["frames"], image, dev)
+            outs.append(_result(image, latent, est, return_latent, return_mask))
+        return outs
+    cap ={} if max_clips is None else {"max_clips": max_clips}   # (a pipe without the parameter keeps working with the default)
     shape = tuple(units[0]["frames"].shape)
     st = []
     for u, uid in zip(units, ids):
@@ -628,6 +790,15 @@ def build_parser():
                    help="how much the source may differ between the two ends of a trajectory, on [0, 1] data (default 0.1)")
     p.add_argument("--stabilize-strength", type=float, default=None, help="in (0, 1]: the weight of a perfectly matching neighbour (default 1)")
     p.add_argument("--stabilize-no-occlusion", action="store_true", help="with --stabilize: no forward-backward consistency check on the trajectories")
+    p.add_argument("--key-stride", type=int, default=None,
+                   help="denoise only every N-th frame (and the last), 2 .. 8, and fill the frames in between along the SOURCE video's optical "
+                        "flow (insv2v/keyfill.py): about N times the delivered frames per GPU second; the flows come from the estimator of "
+                        "--raft-ckpt (--synthetic: key-hashed weights); the --key-* values are starting points, not tuned on real footage")
+    p.add_argument("--key-mode", type=str, default=None,
+                   help="residual (default): carry what the edit CHANGED on the key frames; warp: carry the edited pixels themselves")
+    p.add_argument("--key-sigma", type=float, default=None,
+                   help="how much the source may differ between an in-between frame and its key along a trajectory, on [0, 1] data (default 0.1)")
+    p.add_argument("--key-no-occlusion", action="store_true", help="with --key-stride: no forward-backward consistency check on the trajectories")
     p.add_argument("--synthetic-tiny", action="store_true", help="with --synthetic: the reduced-width UNet / VAE (and scorer) configurations")
     return p
 
@@ -696,6 +867,18 @@ def check_args(args):
             raise SystemExit(f"--stabilize-radius / --stabilize-sigma / --stabilize-strength: {e}")
     elif any(getattr(args, k, None) for k in ("stabilize_radius", "stabilize_sigma", "stabilize_strength", "stabilize_no_occlusion")):
         raise SystemExit("--stabilize-radius / --stabilize-sigma / --stabilize-strength / --stabilize-no-occlusion are parameters of --stabilize")
+    if getattr(args, "key_stride", None) is not None:
+        if not (args.raft_ckpt or args.synthetic):
+            raise SystemExit("--key-stride needs --raft-ckpt FILE (torchvision raft_large weights): the flows the frames in between are filled along come from that estimator")
+        if getattr(args, "auto_mask", False):
+            raise SystemExit("--key-stride and --auto-mask: an estimated mask exists on the key frames only; draw the mask, or track one with --mask-key")
+        from .keyfill import check_fill_args
+        try:
+            check_fill_args(**keyframe_unit(args)["keyframes"])
+        except ValueError as e:
+            raise SystemExit(f"--key-stride / --key-mode / --key-sigma: {e}")
+    elif any(getattr(args, k, None) for k in ("key_mode", "key_sigma", "key_no_occlusion")):
+        raise SystemExit("--key-mode / --key-sigma / --key-no-occlusion are parameters of --key-stride")
     if args.flows and args.units is None and not args.synthetic:
         raise SystemExit("--flows is supported with --units / --synthetic (flows are indexed by unit)")
     score_synth, score_ckpt, score_out = (getattr(args, k, None) for k in ("score_synthetic", "score_ckpt", "score_out"))
@@ -795,6 +978,26 @@ def stabilize_unit(args):
                                occlusion=not getattr(args, "stabilize_no_occlusion", False)))
 
 
+def keyframe_unit(args):
+    """What --key-stride adds to every unit (nothing without it)."""
+    if getattr(args, "key_stride", None) is None:
+        return {}
+    from .keyfill import FILL_DEFAULTS
+    pick = lambda k: FILL_DEFAULTS[k] if getattr(args, "key_" + k, None) is None else getattr(args, "key_" + k)   # noqa: E731
+    return dict(keyframes=dict(stride=args.key_stride, mode=pick("mode"), sigma=pick("sigma"), occlusion=not getattr(args, "key_no_occlusion", False)))
+
+
+def keyframe_record(args, est):
+    """What --key-stride adds to a unit's --score-out record: the stride, the key-frame indices and the mean fill confidence per frame
+    (1 on the key frames; a unit whose frames are all keys has no fill: every frame is listed as a key)."""
+    if getattr(args, "key_stride", None) is None:
+        return {}
+    if est is None or "keys" not in est:
+        return {"key_stride": args.key_stride}
+    return {"key_stride": args.key_stride, "key_frames": [int(k) for k in est["keys"]],
+            "key_confidence": est["confidence"].float().mean((1, 2)).tolist()}
+
+
 def mask_shape_unit(args):
     """What --mask-grow / --mask-feather / --mask-profile / --mask-threshold add to every unit that has a mask (nothing without any of
     them): only the values given, the others keep ``check_shape_args``' defaults."""
@@ -813,7 +1016,7 @@ def load_mask_image(args, width, height):
 
 def mask_region(est, drawn):
     """The region --score-pixels splits a unit by: the shaped mask if the run shaped one, else the tracked / estimated one, else as drawn."""
-    if est is not None:
+    if est is not None and ("shaped" in est or "mask" in est):   # (a key-frame unit's dict may hold only its keys and confidence)
         return est["shaped"] if "shaped" in est else est["mask"]
     return drawn
 
@@ -831,7 +1034,8 @@ def load_mask_file(args):
 def build_flow_estimator(args, device):
     """The CLI's flow estimator of --mask-key, --stabilize and --score-warp (None without any): RAFT on the HIP kernels with the weights of
     --raft-ckpt, key-hashed weights in a --synthetic run."""
-    if getattr(args, "mask_key", None) is None and not getattr(args, "score_warp", False) and not getattr(args, "stabilize", False):
+    if getattr(args, "mask_key", None) is None and not getattr(args, "score_warp", False) and not getattr(args, "stabilize", False) \
+            and getattr(args, "key_stride", None) is None:
         return None
     from .raft import RAFTFlow
     if args.raft_ckpt:
@@ -844,7 +1048,7 @@ def write_masks(path, records, rank=0, world=1):
     """{unit id: {"mask_latent": [T,h,w], "soft": [T,h,w]}} (estimated, --auto-mask) or {unit id: {"mask": [T,H,W], "valid": [T,H,W]}}
     (tracked, --mask-key) of this rank's units (with several ranks each writes its own FILE.rankR.pt).  A shaped run (--mask-grow /
     --mask-feather) writes every unit's "shaped" and "support" [T,H,W] next to whatever its source returned."""
-    records = {u: est for u, est in records.items() if est is not None}   # (a unit the mask file does not name has none)
+    records = {u: est for u, est in records.items() if est is not None and set(est) - {"keys", "confidence"}}   # (a unit the mask file does not name has none)
     if any("shaped" in est for est in records.values()):   # --mask-grow / --mask-feather: what the source gave, and the two shaped masks
         if world > 1:
             root, ext = os.path.splitext(path)
@@ -903,9 +1107,10 @@ def run_dataset(args, model, pipe, rank=0, world=1, scorer=None):
     auto = auto_mask_unit(args)
     track, drawn = mask_track_unit(args), load_mask_file(args)   # drawn masks are named by video here
     estimator = build_flow_estimator(args, model.unet.device)
-    stab, shape = stabilize_unit(args), mask_shape_unit(args)
-    more = {"flow_estimator": estimator} if track or stab else {}
-    want_masks = {"return_mask": True} if (auto or track or shape) and (getattr(args, "mask_out", None) or getattr(args, "score_pixels", False)) else {}   # (a plain run carries no new keyword)
+    stab, shape, keyf = stabilize_unit(args), mask_shape_unit(args), keyframe_unit(args)
+    more = {"flow_estimator": estimator} if track or stab or keyf else {}
+    want_masks = {"return_mask": True} if ((auto or track or shape) and (getattr(args, "mask_out", None) or getattr(args, "score_pixels", False))) \
+        or (keyf and getattr(args, "score_out", None)) else {}   # (a plain run carries no new keyword)
     masks = {}
     for ci, (video_id, text_cfg, video_cfg, num_frames, image_size) in enumerate(combos):
         if ci % world != rank:
@@ -928,7 +1133,7 @@ def run_dataset(args, model, pipe, rank=0, world=1, scorer=None):
                 continue
             todo.append((gif_path, image_dir, dict(frames=frames, text_cond=model.encode_text([prompt]), text_uncond=text_uncond,
                                                    text_cfg=text_cfg, video_cfg=video_cfg, cond=cond, unit=4 * ci + kinds.index(key),
-                                                   strength=getattr(args, "strength", 1.0), **auto, **stab,
+                                                   strength=getattr(args, "strength", 1.0), **auto, **stab, **keyf,
                                                    **(shape if auto or batch["video_name"] in drawn else {}),
                                                    **(dict(mask=drawn[batch["video_name"]], mask_mode=getattr(args, "mask_mode", "max"),
                                                            **track) if batch["video_name"] in drawn else {})), prompt))
@@ -946,6 +1151,7 @@ def run_dataset(args, model, pipe, rank=0, world=1, scorer=None):
             if want_pixel_scores(args):   # the region: the unit's image-resolution mask - tracked or estimated if the run made one, else as drawn
                 est = masks.get(u["unit"])
                 rec.update(pixel_record(args, frames, edited, mask_region(est, u.get("mask")), estimator))
+            rec.update(keyframe_record(args, masks.get(u["unit"])))
             records.append(rec)
             save_tensor_to_gif(torch.cat([frames.float().cpu(), edited.float().cpu()], dim=4), gif_path, fps=5)
             save_tensor_to_images(edited.float().cpu(), image_dir)
@@ -1027,15 +1233,15 @@ def main(argv=None):
     if track and not drawn and image_mask is None and data.get("mask") is None:
         raise SystemExit("--mask-key needs a mask to track: --mask-file FILE.pt, the \"mask\" entry of a --units file, or --synthetic-mask")
     estimator = build_flow_estimator(args, f"cuda:{local}")
-    stab, shape = stabilize_unit(args), mask_shape_unit(args)
-    more = {"flow_estimator": estimator} if track or stab else {}
-    want_masks = {"return_mask": True} if (auto or track or shape) and (args.mask_out or args.score_pixels) else {}
+    stab, shape, keyf = stabilize_unit(args), mask_shape_unit(args), keyframe_unit(args)
+    more = {"flow_estimator": estimator} if track or stab or keyf else {}
+    want_masks = {"return_mask": True} if ((auto or track or shape) and (args.mask_out or args.score_pixels)) or (keyf and args.score_out) else {}
     est_masks = {}
     masks = data.get("mask")   # optional [n,T,H,W] / [n,1,H,W]
 
     def edit(i):
         m = masks[i:i + 1] if masks is not None else drawn.get(i, image_mask)
-        return dict(dict(mask=m, strength=args.strength, mask_mode=args.mask_mode), **auto, **stab, **(track if m is not None else {}),
+        return dict(dict(mask=m, strength=args.strength, mask_mode=args.mask_mode), **auto, **stab, **keyf, **(track if m is not None else {}),
                     **(shape if m is not None or auto else {}))
     scorer = build_scorer(args, f"cuda:{local}", tok)
     records = []
@@ -1069,6 +1275,7 @@ def main(argv=None):
             if want_pixel_scores(args):   # the region: the unit's image-resolution mask - tracked or estimated if the run made one, else as drawn
                 est = est_masks.get(ci * n + i)
                 rec.update(pixel_record(args, data["frames"][i:i + 1], edited, mask_region(est, edit(i)["mask"]), estimator))
+            rec.update(keyframe_record(args, est_masks.get(ci * n + i)))
             records.append(rec)
         local_out = torch.cat(local_out, 0).half() if local_out else torch.zeros((0, *item_shape), device=model.unet.device).half()
         outs.append(gather_frames(local_out, n, item_shape=item_shape))
