@@ -74,6 +74,16 @@ STABILIZE_KEYS = ("radius", "sigma", "strength", "occlusion", "alpha", "beta")
 KEYFRAME_KEYS = ("stride", "mode", "sigma", "occlusion", "alpha", "beta")
 
 
+# The per-unit keywords of an edit, listed ONCE: keywords of ``edit_video``, entries of a unit of ``edit_videos``, the arguments an
+# ``_EditUnit`` is built from.  A new per-unit feature adds its keywords here (and to ``edit_video``'s signature).  The second row is
+# what ``check_edit_args`` checks, in its parameters' order.
+UNIT_KEYS = ("text_cfg", "video_cfg", "init_noises", "enc_noise", "cond", "flows_per_window",
+             "mask", "strength", "mask_mode", "auto_mask", "mask_key", "mask_flows", "mask_track", "stabilize", "stabilize_flows", "mask_shape",
+             "keyframes", "key_flows")
+CHECKED_KEYS = UNIT_KEYS[6:]
+UNIT_DEFAULTS = dict({k: None for k in UNIT_KEYS}, text_cfg=7.5, video_cfg=1.8, strength=1.0, mask_mode="max")
+
+
 def check_edit_args(frames_shape, mask=None, strength=1.0, mask_mode="max", auto_mask=None, mask_key=None, mask_flows=None, mask_track=None,
                     stabilize=None, stabilize_flows=None, mask_shape=None, keyframes=None, key_flows=None):
     """Host-side check of the localized / partial edit controls (nothing is launched): ``strength`` in (0, 1], ``mask_mode`` "mean" or
@@ -87,20 +97,28 @@ def check_edit_args(frames_shape, mask=None, strength=1.0, mask_mode="max", auto
     the mask of any source, so it needs one.  ``keyframes`` (None, an int stride or a dict with keys among ``KEYFRAME_KEYS``) optionally
     with ``key_flows``, a dict(fwd=, bwd=) of the source video's [T-1,2,H,W] flows; not together with ``mask="auto"`` (an estimated mask
     exists on the key frames only)."""
-    strength_to_start(strength, 1)
-    _check_keyframe_args(frames_shape, mask, keyframes, key_flows)
-    if mask_shape is not None:
+    _check_unit(frames_shape, locals())
+
+
+def _check_unit(frames_shape, u):
+    """``check_edit_args`` of a unit's arguments by name (the missing ones at their defaults).  The refusals in their order: key
+    frames, ``mask_shape``, ``stabilize``, the tracked mask, ``mask_mode``, ``auto_mask``, the mask itself."""
+    a = {k: u.get(k, UNIT_DEFAULTS[k]) for k in CHECKED_KEYS}
+    mask, auto_mask = a["mask"], a["auto_mask"]
+    strength_to_start(a["strength"], 1)
+    _check_keyframe_args(frames_shape, mask, a["keyframes"], a["key_flows"])
+    if a["mask_shape"] is not None:
         from .mask_shape import check_mask_shape
-        check_mask_shape(mask_shape)
+        check_mask_shape(a["mask_shape"])
         if mask is None:
             raise ValueError("mask_shape shapes the mask of a localized edit: pass mask= (a tensor, \"auto\", or with mask_key=) with it")
-    _check_stabilize_args(frames_shape, stabilize, stabilize_flows)
-    if mask_key is None and (mask_flows is not None or mask_track is not None):
+    _check_stabilize_args(frames_shape, a["stabilize"], a["stabilize_flows"])
+    if a["mask_key"] is None and (a["mask_flows"] is not None or a["mask_track"] is not None):
         raise ValueError("mask_flows / mask_track belong to a tracked mask: pass mask_key=, the frame the mask is drawn on, with them")
-    if mask_key is not None:
-        _check_track_args(frames_shape, mask, mask_key, mask_flows, mask_track)
-    if mask_mode not in MASK_MODES:
-        raise ValueError(f"mask_mode {mask_mode!r} is neither 'mean' nor 'max'")
+    if a["mask_key"] is not None:
+        _check_track_args(frames_shape, mask, a["mask_key"], a["mask_flows"], a["mask_track"])
+    if a["mask_mode"] not in MASK_MODES:
+        raise ValueError(f"mask_mode {a['mask_mode']!r} is neither 'mean' nor 'max'")
     if auto_mask is not None and not (isinstance(mask, str) and mask == "auto"):
         raise ValueError("auto_mask holds the parameters of an estimated mask: pass mask=\"auto\" with it")
     if isinstance(mask, str):
@@ -111,12 +129,8 @@ def check_edit_args(frames_shape, mask=None, strength=1.0, mask_mode="max", auto
             raise ValueError(f"mask=\"auto\" needs frames [1,T,3,H,W] with H and W multiples of 8 (one latent cell per 8x8 pixels), not {tuple(frames_shape)}")
         if auto_mask is not None:
             from .inference import check_automask_args
-            if not isinstance(auto_mask, dict) or set(auto_mask) - set(AUTO_MASK_KEYS):
-                raise ValueError(f"auto_mask (the parameters of mask=\"auto\") must be a dict with keys among {AUTO_MASK_KEYS}, got {auto_mask!r}")
-            try:
-                check_automask_args(**{k: v for k, v in auto_mask.items() if k != "noises"})
-            except ValueError as e:
-                raise ValueError(f"auto_mask (the parameters of mask=\"auto\"): {e}") from None
+            _check_params("auto_mask (the parameters of mask=\"auto\")", auto_mask, AUTO_MASK_KEYS,
+                          lambda **kw: check_automask_args(**{k: v for k, v in kw.items() if k != "noises"}))
         return
     if mask is None:
         return
@@ -129,6 +143,27 @@ def check_edit_args(frames_shape, mask=None, strength=1.0, mask_mode="max", auto
         raise ValueError(f"a mask needs frame sizes that are multiples of 8 (one latent cell per 8x8 pixels), not {H}x{W}")
 
 
+def _check_params(name, params, keys, check, form=None):
+    """A feature's dict of parameters: its keys among ``keys``, its values accepted by the feature's own ``check``."""
+    if not isinstance(params, dict) or set(params) - set(keys):
+        raise ValueError(f"{name} must be a dict with keys among {keys}, got {params!r}" if form is None else form)
+    try:
+        check(**params)
+    except ValueError as e:
+        raise ValueError(f"{name}: {e}") from None
+
+
+def _check_flow_dict(name, flows, frames_shape, required, form):
+    """``flows``, the argument ``name``, as a dict(fwd=, bwd=) of floating-point [T-1,2,H,W] flows for frames [1,T,3,H,W]; ``required``:
+    the directions that must be there, ``form``: what the refusal says the dict holds."""
+    T, H, W = frames_shape[1], frames_shape[3], frames_shape[4]
+    if not isinstance(flows, dict) or not flows or set(flows) - {"fwd", "bwd"} or any(flows.get(k) is None for k in required):
+        raise ValueError(f"{name} must be a dict(fwd=, bwd=) of {form}")
+    for k, f in flows.items():
+        if f is not None and (not torch.is_tensor(f) or not f.is_floating_point() or tuple(f.shape) != (T - 1, 2, H, W)):
+            raise ValueError(f"{name}[{k!r}] {tuple(getattr(f, 'shape', ()))} must be a floating-point [{T - 1},2,{H},{W}] for frames {tuple(frames_shape)}")
+
+
 def _check_track_args(frames_shape, mask, mask_key, mask_flows, mask_track):
     """The ``mask_key`` part of ``check_edit_args``."""
     from .mask_track import check_track_args
@@ -138,20 +173,10 @@ def _check_track_args(frames_shape, mask, mask_key, mask_flows, mask_track):
     if isinstance(mask_key, bool) or not isinstance(mask_key, int) or not 0 <= mask_key < T:
         raise ValueError(f"mask_key {mask_key!r} is not a frame index of a video of {T} frames")
     track = {} if mask_track is None else mask_track
-    if not isinstance(track, dict) or set(track) - set(MASK_TRACK_KEYS):
-        raise ValueError(f"mask_track (the parameters of a tracked mask) must be a dict with keys among {MASK_TRACK_KEYS}, got {mask_track!r}")
-    try:
-        check_track_args(**track)
-    except ValueError as e:
-        raise ValueError(f"mask_track (the parameters of a tracked mask): {e}") from None
+    _check_params("mask_track (the parameters of a tracked mask)", track, MASK_TRACK_KEYS, check_track_args)
     if mask_flows is not None:
-        if not isinstance(mask_flows, dict) or set(mask_flows) - {"fwd", "bwd"} or not mask_flows:
-            raise ValueError(f"mask_flows must be a dict(fwd=, bwd=) of [{T - 1},2,{H},{W}] flows")
-        for k, f in mask_flows.items():
-            if f is not None and (not torch.is_tensor(f) or tuple(f.shape) != (T - 1, 2, H, W)):
-                raise ValueError(f"mask_flows[{k!r}] {tuple(getattr(f, 'shape', ()))} must be [{T - 1},2,{H},{W}] for frames {tuple(frames_shape)}")
-        if track.get("occlusion", True) and T > 1 and (mask_flows.get("fwd") is None or mask_flows.get("bwd") is None):
-            raise ValueError("mask_flows: the occlusion check of a tracked mask needs both fwd and bwd (or mask_track=dict(occlusion=False))")
+        _check_flow_dict("mask_flows", mask_flows, frames_shape, ("fwd", "bwd") if track.get("occlusion", True) and T > 1 else (),
+                         f"[{T - 1},2,{H},{W}] flows (the occlusion check of a tracked mask needs both fwd and bwd, or mask_track=dict(occlusion=False))")
 
 
 def _stabilize_params(stabilize):
@@ -169,22 +194,14 @@ def _check_stabilize_args(frames_shape, stabilize, stabilize_flows):
         if stabilize_flows is not None:
             raise ValueError("stabilize_flows belongs to a stabilized edit: pass stabilize=True (or a dict of its parameters) with it")
         return
-    if not isinstance(params, dict) or set(params) - set(STABILIZE_KEYS):
-        raise ValueError(f"stabilize must be None, True or a dict with keys among {STABILIZE_KEYS}, got {stabilize!r}")
-    try:
-        check_filter_args(**params)
-    except ValueError as e:
-        raise ValueError(f"stabilize (the parameters of the temporal filter): {e}") from None
+    _check_params("stabilize (the parameters of the temporal filter)", params, STABILIZE_KEYS, check_filter_args,
+                  f"stabilize must be None, True or a dict with keys among {STABILIZE_KEYS}, got {stabilize!r}")
     b, T, _, H, W = frames_shape
     if b != 1:
         raise ValueError(f"stabilize needs frames [1,T,3,H,W], not {tuple(frames_shape)}")
     if stabilize_flows is not None:
-        if not isinstance(stabilize_flows, dict) or set(stabilize_flows) - {"fwd", "bwd"} or stabilize_flows.get("fwd") is None \
-                or (params.get("occlusion", True) and stabilize_flows.get("bwd") is None):
-            raise ValueError(f"stabilize_flows must be a dict(fwd=, bwd=) of the source video's [{T - 1},2,{H},{W}] flows (bwd may be missing with occlusion=False)")
-        for k, f in stabilize_flows.items():
-            if f is not None and (not torch.is_tensor(f) or not f.is_floating_point() or tuple(f.shape) != (T - 1, 2, H, W)):
-                raise ValueError(f"stabilize_flows[{k!r}] {tuple(getattr(f, 'shape', ()))} must be a floating-point [{T - 1},2,{H},{W}] for frames {tuple(frames_shape)}")
+        _check_flow_dict("stabilize_flows", stabilize_flows, frames_shape, ("fwd", "bwd") if params.get("occlusion", True) else ("fwd",),
+                         f"the source video's [{T - 1},2,{H},{W}] flows (bwd may be missing with occlusion=False)")
 
 
 def _keyframe_params(keyframes):
@@ -202,12 +219,8 @@ def _check_keyframe_args(frames_shape, mask, keyframes, key_flows):
         if key_flows is not None:
             raise ValueError("key_flows belongs to a key-frame edit: pass keyframes= (a stride, or a dict of its parameters) with it")
         return
-    if not isinstance(params, dict) or set(params) - set(KEYFRAME_KEYS):
-        raise ValueError(f"keyframes must be None, an int stride or a dict with keys among {KEYFRAME_KEYS}, got {keyframes!r}")
-    try:
-        check_fill_args(**params)
-    except ValueError as e:
-        raise ValueError(f"keyframes (the parameters of the key-frame edit): {e}") from None
+    _check_params("keyframes (the parameters of the key-frame edit)", params, KEYFRAME_KEYS, check_fill_args,
+                  f"keyframes must be None, an int stride or a dict with keys among {KEYFRAME_KEYS}, got {keyframes!r}")
     b, T, _, H, W = frames_shape
     if b != 1:
         raise ValueError(f"keyframes needs frames [1,T,3,H,W], not {tuple(frames_shape)}")
@@ -215,84 +228,47 @@ def _check_keyframe_args(frames_shape, mask, keyframes, key_flows):
         raise ValueError("keyframes and mask=\"auto\": an estimated mask exists on the key frames only (carrying it to the frames in between "
                          "is not built); draw the mask, or track one with mask_key=")
     if key_flows is not None:
-        if not isinstance(key_flows, dict) or set(key_flows) - {"fwd", "bwd"} or key_flows.get("fwd") is None or key_flows.get("bwd") is None:
-            raise ValueError(f"key_flows must be a dict(fwd=, bwd=) of the source video's [{T - 1},2,{H},{W}] flows (the previous key is reached along bwd, the next along fwd)")
-        for k, f in key_flows.items():
-            if not torch.is_tensor(f) or not f.is_floating_point() or tuple(f.shape) != (T - 1, 2, H, W):
-                raise ValueError(f"key_flows[{k!r}] {tuple(getattr(f, 'shape', ()))} must be a floating-point [{T - 1},2,{H},{W}] for frames {tuple(frames_shape)}")
+        _check_flow_dict("key_flows", key_flows, frames_shape, ("fwd", "bwd"),
+                         f"the source video's [{T - 1},2,{H},{W}] flows (the previous key is reached along bwd, the next along fwd)")
 
 
-_FULL_RATE_ONLY = ("keyframes", "key_flows", "mask_key", "mask_flows", "mask_track", "stabilize", "stabilize_flows")
+_NO_FLOW_SOURCE = {
+    "keyframes": "key-frame edit (keyframes=) without a flow source: pass key_flows=, stabilize_flows=, mask_flows= or flow_estimator=, or build the pipe with flow_estimator=",
+    "stabilize": "stabilized edit (stabilize=) without a flow source: pass stabilize_flows=, mask_flows= or flow_estimator=, or build the pipe with flow_estimator=",
+    "mask_key": "tracked mask (mask_key=) without a flow source: pass mask_flows= or flow_estimator=, or build the pipe with flow_estimator=",
+}
 
 
-def _keyframe_prepare(inf_pipe, frames, kf, u, flow_estimator, dev):
-    """``keyframes=``: what a unit needs before the first window of its key frames -> None when every frame is a key (the unit is then
-    edited as if ``keyframes`` were not given), else (changed, state): ``changed`` holds the arguments of ``edit_video`` that the
-    sub-video of the key frames takes in place of the unit's (``frames``, ``cond``, ``enc_noise``, ``mask``; the arguments of
-    ``_FULL_RATE_ONLY`` are dropped), ``state`` what ``_keyframe_finish`` needs.  ``u``: the unit's arguments by name.  The source video's
-    flows - ``key_flows``, ``stabilize_flows``, ``mask_flows`` (each when it holds both sets), ``flow_estimator``, the pipe's own
-    estimator, in this order - are computed at most once, at full rate, and serve the fill, a tracked mask and the filter; a ``mask_key``
-    mask is tracked over the FULL-RATE video."""
-    from .keyfill import key_frames, FILL_DEFAULTS
+def _both(flows):
+    """A flow dict that holds both directions, else None: only such a dict can stand in for another feature's flows."""
+    return flows if flows is not None and flows.get("fwd") is not None and flows.get("bwd") is not None else None
+
+
+def _source_flows(inf_pipe, frames, candidates, flow_estimator, feature, both=True, key=None):
+    """The source video's adjacent-frame flows a feature of one unit follows -> (dict(fwd, bwd), whether they were computed here); (None,
+    False) for a single frame, which needs no flow.  In this order: the first of ``candidates`` that is not None, ``flow_estimator``, the
+    pipe's own estimator - then ONE ``mask_track.pair_flows`` of the whole unit (``both=False`` with ``key``: only the pairs the chain
+    from ``key`` reads).  ``feature`` names the RuntimeError of a unit without any source."""
+    if frames.shape[1] == 1:
+        return None, False
+    given = next((f for f in candidates if f is not None), None)
+    if given is not None:
+        return given, False
+    est = flow_estimator if flow_estimator is not None else getattr(inf_pipe, "flow_estimator", None)
+    if est is None:
+        raise RuntimeError(_NO_FLOW_SOURCE[feature])
     from .mask_track import pair_flows
-    T = frames.shape[1]
-    keys = key_frames(T, kf.get("stride", FILL_DEFAULTS["stride"]))
-    if len(keys) == T:
-        return None
-    both = lambda f: f is not None and f.get("fwd") is not None and f.get("bwd") is not None   # noqa: E731
-    flows = next((f for f in (u.get("key_flows"), u.get("stabilize_flows"), u.get("mask_flows")) if both(f)), None)
-    if flows is None:
-        est = flow_estimator if flow_estimator is not None else getattr(inf_pipe, "flow_estimator", None)
-        if est is None:
-            raise RuntimeError("key-frame edit (keyframes=) without a flow source: pass key_flows=, stabilize_flows=, mask_flows= or flow_estimator=, or build the pipe with flow_estimator=")
-        flows = pair_flows(frames, est, both=True)
-    mask, est, shape = u.get("mask"), None, None
-    if u.get("mask_key") is not None:
-        est = _track_mask(inf_pipe, frames, mask, u["mask_key"], u["mask_flows"] if u.get("mask_flows") is not None else flows, flow_estimator,
-                          u.get("mask_track"), dev)
-        mask = est["mask"]
-    mask_img = None
-    if mask is not None:   # the full-rate mask of the composite, shaped per frame exactly as the sub-video's plan shapes its rows
-        mask_img = mask.to(device=dev, dtype=torch.float32).expand(1, T, *mask.shape[2:])[0].contiguous()
-        if u.get("mask_shape") is not None:
-            from .mask_shape import shape_mask
-            mask_img, support = shape_mask(mask_img, **u["mask_shape"])
-            shape = dict(shaped=mask_img[None], support=support[None])
-    changed = dict(frames=frames[:, keys])
-    for k in ("cond", "enc_noise"):
-        if u.get(k) is not None:
-            changed[k] = u[k][:, keys]
-    if mask is not None:
-        changed["mask"] = mask if mask.shape[1] == 1 else mask[:, keys]
-    stab = _stabilize_params(u.get("stabilize"))
-    state = dict(kf=kf, keys=keys, flows=flows, mask_img=mask_img, est=est if shape is None else dict(est or {}, **shape), stab=stab,
-                 sflows=u["stabilize_flows"] if u.get("stabilize_flows") is not None else flows)
-    return changed, state
-
-
-def _keyframe_finish(state, frames, key_image, dev):
-    """The edited key frames [1,Tk,3,H,W] of a unit -> (its full-rate result [1,T,3,H,W], the ``return_mask`` dict): the frames in
-    between are filled along the source's flow (``keyfill.keyframe_fill``), with a mask each of them is composited against the input
-    with its own mask exactly as the key frames were (``ops.composite``), and ``stabilize`` runs once, on the full-rate result.  The key
-    frames stay ``key_image``'s bit for bit unless the filter runs."""
-    from .keyfill import keyframe_fill
-    kf, keys = state["kf"], state["keys"]
-    fill = keyframe_fill(frames, key_image, keys, flows=state["flows"], **{k: kf[k] for k in ("mode", "sigma", "occlusion", "alpha", "beta") if k in kf})
-    image = fill["frames"]
-    if state["mask_img"] is not None:
-        rows = torch.tensor([t for t in range(frames.shape[1]) if t not in keys], dtype=torch.long, device=image.device)
-        img = image[0].index_select(0, rows).to(torch.float32).contiguous()
-        orig = frames[0].to(device=img.device, dtype=torch.float32).index_select(0, rows).contiguous()
-        img = ops.composite(img, orig, state["mask_img"].index_select(0, rows).contiguous(), out=img)
-        image[0].index_copy_(0, rows, img.to(image.dtype))
-    if state["stab"] is not None:
-        image = _stabilize(frames, image, state["stab"], state["sflows"], state["mask_img"])
-    return image, dict(state["est"] or {}, keys=list(keys), confidence=fill["confidence"])
+    return pair_flows(frames, est, both=both, key=key), True
 
 
 def _start_time(inf_pipe, strength):
     """``start_time`` of an edit of this strength (full strength asks the pipe nothing: any pipe object keeps working)."""
     return 0 if strength == 1.0 else strength_to_start(strength, inf_pipe.num_ddim_steps)[1]
+
+
+def _image_mask(mask, T, dev):
+    """A unit's mask [1,T,H,W] or [1,1,H,W] -> one fp32 mask per frame [T,H,W] on the device."""
+    return mask.to(device=dev, dtype=torch.float32).expand(1, T, *mask.shape[2:])[0].contiguous()
 
 
 class _EditPlan:
@@ -314,8 +290,7 @@ class _EditPlan:
         if partial:
             self.level = inf_pipe.scheduler.start_coefficients(int(inf_pipe.scheduler.timesteps[self.start_time]))
         if mask is not None:
-            T = frames.shape[1]
-            self.mask_img = mask.to(device=dev, dtype=torch.float32).expand(1, T, *mask.shape[2:])[0].contiguous()   # [T,H,W]
+            self.mask_img = _image_mask(mask, frames.shape[1], dev)
             if mask_shape is None:
                 latent_mask = ops.mask_to_latent(self.mask_img, mask_mode)
             else:   # two masks: the soft one for the composite, the hard region under it - the whole feather - for the latent hold
@@ -349,50 +324,6 @@ class _EditPlan:
         return ops.composite(img, orig, self.mask_img, out=img)[None]
 
 
-def _estimate_mask(model, inf_pipe, z, cond, text_cond, text_uncond, frames_in_batch, auto_mask, seed, unit):
-    """``mask="auto"``: the unit's mask, estimated ONCE from the whole video in launches of its own, before its first window
-    (``InferenceIP2PVideo.estimate_mask``) -> its result dict; ``["mask"]`` [1,T,H,W] then goes through ``_EditPlan`` like a user's."""
-    if z is None:   # (a caller's ``cond`` is z / scale_factor)
-        z = cond * model.scale_factor
-    kw = dict(frames_in_batch=frames_in_batch)
-    kw.update(auto_mask or {})
-    return inf_pipe.estimate_mask(z, text_cond, text_uncond, cond, **kw, **_seeded(seed, unit))
-
-
-def _track_mask(inf_pipe, frames, mask, mask_key, mask_flows, flow_estimator, mask_track, dev):
-    """``mask_key=``: the unit's mask, tracked ONCE from the whole video in launches of its own, before its first window
-    (``mask_track.propagate_mask``) -> its result dict; ``["mask"]`` [1,T,H,W] then goes through ``_EditPlan`` like a user's."""
-    from .mask_track import pair_flows, propagate_mask
-    track = dict(mask_track or {})
-    T = frames.shape[1]
-    if mask_flows is None and T > 1:
-        est = flow_estimator if flow_estimator is not None else getattr(inf_pipe, "flow_estimator", None)
-        if est is None:
-            raise RuntimeError("tracked mask (mask_key=) without a flow source: pass mask_flows= or flow_estimator=, or build the pipe with flow_estimator=")
-        mask_flows = pair_flows(frames, est, both=track.get("occlusion", True), key=mask_key)
-    if T == 1:   # nothing to track: no flow is needed, none is launched
-        mask_flows = {k: torch.zeros((0, 2, *frames.shape[-2:]), device=dev) for k in ("fwd", "bwd")}
-    flows = {k: (None if mask_flows.get(k) is None else mask_flows[k].to(device=dev, dtype=torch.float32)) for k in ("fwd", "bwd")}
-    return propagate_mask(mask.to(device=dev), mask_key, flows["fwd"], flows["bwd"], **track)
-
-
-def _stabilize_flows(inf_pipe, frames, params, stabilize_flows, mask_flows, flow_estimator):
-    """``stabilize=``: the source video's flows the filter follows -> (dict(fwd, bwd) or None for a single frame, whether they were
-    computed here).  In this order: ``stabilize_flows``, the ``mask_flows`` of a tracked mask when they hold both sets, ``flow_estimator``,
-    the pipe's own estimator - then ONE ``pair_flows(both=True)`` of the whole unit, which also serves its tracked mask."""
-    from .mask_track import pair_flows
-    if frames.shape[1] == 1:   # nothing to filter: no flow is needed, none is computed
-        return None, False
-    if stabilize_flows is not None:
-        return stabilize_flows, False
-    if mask_flows is not None and mask_flows.get("fwd") is not None and mask_flows.get("bwd") is not None:
-        return mask_flows, False
-    est = flow_estimator if flow_estimator is not None else getattr(inf_pipe, "flow_estimator", None)
-    if est is None:
-        raise RuntimeError("stabilized edit (stabilize=) without a flow source: pass stabilize_flows=, mask_flows= or flow_estimator=, or build the pipe with flow_estimator=")
-    return pair_flows(frames, est, both=True), True
-
-
 def _stabilize(frames, image, params, flows, mask_img):
     """The unit's finished frames [1,T,3,H,W], filtered once over the whole unit - also across the hand-over of its windows."""
     from .temporal_filter import stabilize
@@ -401,10 +332,149 @@ def _stabilize(frames, image, params, flows, mask_img):
     return stabilize(frames, image, flows=flows, mask=None if mask_img is None else mask_img[None], **params)
 
 
-def _with_shape(est, plan):
-    """``return_mask``'s dict of a unit: with ``mask_shape`` it gains ``shaped`` and ``support`` [1,T,H,W] (a drawn mask has no dict
-    before that)."""
-    return est if plan.shape is None else dict(est or {}, **plan.shape)
+class _EditUnit:
+    """One (video, prompt) unit, as BOTH drivers run it: ``edit_video`` drives one, ``edit_videos`` several in step, and what a unit
+    does - in which order, with which arguments - is written here only.  ``args``: the unit's arguments by name (``UNIT_KEYS``; the
+    missing ones take ``UNIT_DEFAULTS``).  Three phases:
+
+      ``prepare()``   once, before the first window: the source video's flows, the tracked mask, the key-frame reduction, the VAE encode,
+                      the estimated mask, the ``_EditPlan``, the window split.  Everything that can refuse refuses here, flows first -
+                      a missing flow source raises before anything is sampled.
+      ``window(k)``   the keywords of the pipe call of window k (``first()`` for k = 0, ``second_clip_forward`` / ``run_stacked`` after);
+                      ``receive(k, out)`` takes that call's result.
+      ``finish()``    after the last window: decode, composite, fill the frames between the keys, stabilize -> (image, latent, est).
+
+    A new per-unit feature plugs in here: its keywords join ``UNIT_KEYS``, its check ``_check_unit``, and its work goes into the phase it
+    belongs to - both drivers get it at once.  The unit's constructor runs nothing and touches neither model nor pipe; it only works out
+    which frames are sampled (``keys``; None: all of them) and their shape."""
+
+    def __init__(self, model, inf_pipe, frames, text_cond, text_uncond, frames_in_batch, num_ref_frames, seed, unit, flow_estimator, args,
+                 number_first_window=False):
+        from .keyfill import key_frames, FILL_DEFAULTS
+        self.model, self.pipe, self.source, self.text = model, inf_pipe, frames, dict(text_cond=text_cond, text_uncond=text_uncond)
+        self.fib, self.nref, self.seed, self.unit, self.estimator = frames_in_batch, num_ref_frames, seed, unit, flow_estimator
+        self.a = dict(UNIT_DEFAULTS, **args)
+        self.number_first = number_first_window   # (edit_video has always sent its first window without ``window=0``)
+        self.kf, self.keys = _keyframe_params(self.a["keyframes"]), None
+        if self.kf is not None:
+            keys = key_frames(frames.shape[1], self.kf.get("stride", FILL_DEFAULTS["stride"]))
+            self.keys = keys if len(keys) < frames.shape[1] else None   # every frame a key: edited as if ``keyframes`` were not given
+        self.shape = tuple(frames.shape) if self.keys is None else (frames.shape[0], len(self.keys), *frames.shape[2:])
+
+    def prepare(self):
+        from .mask_track import propagate_mask
+        a, model, pipe, source = self.a, self.model, self.pipe, self.source
+        dev = self.dev = model.unet.device
+        T = source.shape[1]
+        # the source video's flows: at most ONE full-rate pair_flows(both=True) serves the fill, the filter and a tracked mask
+        shared = None
+        if self.keys is not None:
+            shared, _ = _source_flows(pipe, source, [_both(a["key_flows"]), _both(a["stabilize_flows"]), _both(a["mask_flows"])], self.estimator, "keyframes")
+        self.fill_flows = shared
+        self.stab, self.stab_flows = _stabilize_params(a["stabilize"]), None
+        if self.stab is not None:
+            self.stab_flows, computed = _source_flows(pipe, source, [a["stabilize_flows"], shared, _both(a["mask_flows"])], self.estimator, "stabilize")
+            if computed:
+                shared = self.stab_flows
+        mask, est = a["mask"], None
+        if a["mask_key"] is not None:   # tracked ONCE over the full-rate video, in launches of its own; from there a user's [1,T,H,W] mask
+            track = dict(a["mask_track"] or {})
+            flows, _ = _source_flows(pipe, source, [a["mask_flows"], shared], self.estimator, "mask_key", both=track.get("occlusion", True), key=a["mask_key"])
+            if flows is None:   # a single frame: nothing to track, no flow is needed, none is launched
+                flows = {k: torch.zeros((0, 2, *source.shape[-2:]), device=dev) for k in ("fwd", "bwd")}
+            fwd, bwd = (None if flows.get(k) is None else flows[k].to(device=dev, dtype=torch.float32) for k in ("fwd", "bwd"))
+            est = propagate_mask(mask.to(device=dev), a["mask_key"], fwd, bwd, **track)
+            mask = est["mask"]
+        # the key-frame reduction: from here the unit's windows see the sub-video of its keys
+        frames, cond, enc_noise = source, a["cond"], a["enc_noise"]
+        self.full_mask = None
+        if self.keys is not None:
+            if mask is not None:   # the full-rate mask of the composite, shaped per frame exactly as the plan shapes the keys' rows
+                self.full_mask = _image_mask(mask, T, dev)
+                if a["mask_shape"] is not None:
+                    from .mask_shape import shape_mask
+                    self.full_mask, support = shape_mask(self.full_mask, **a["mask_shape"])
+                    est = dict(est or {}, shaped=self.full_mask[None], support=support[None])
+                mask = mask if mask.shape[1] == 1 else mask[:, self.keys]
+            frames = source[:, self.keys]
+            cond, enc_noise = (None if t is None else t[:, self.keys] for t in (cond, enc_noise))
+        self.frames = frames
+        z = None
+        if cond is None:
+            z = model.encode_image_to_latent(frames, enc_noise, **_seeded(self.seed, self.unit))
+            cond = z / model.scale_factor
+        if isinstance(mask, str):   # "auto" (check_edit_args): estimated ONCE from the whole video, in launches of its own
+            kw = dict(dict(frames_in_batch=self.fib), **(a["auto_mask"] or {}))
+            est = pipe.estimate_mask(cond * model.scale_factor if z is None else z, self.text["text_cond"], self.text["text_uncond"], cond,
+                                     **kw, **_seeded(self.seed, self.unit))
+            mask = est["mask"]
+        self.plan = _EditPlan(model, pipe, frames, cond, mask, a["strength"], a["mask_mode"], self.fib, self.nref, z=z, mask_shape=a["mask_shape"])
+        if self.keys is None and self.plan.shape is not None:   # return_mask gains shaped / support (a drawn mask has no dict before that)
+            est = dict(est or {}, **self.plan.shape)
+        self.est = est
+        self.conds, self.refs = split_batch(cond, self.fib, self.nref)
+        self.windows = len(self.conds)
+        self.wants_flow = hasattr(pipe, "obtain_flow_batched")
+        if self.wants_flow and a["flows_per_window"] is None and getattr(pipe, "flow_estimator", None) is None and self.windows > 1:
+            raise RuntimeError("optical-flow pipeline without a flow source: pass flows_per_window= or build the pipe with flow_estimator=")
+        self.frame_chunks = split_batch(frames, self.fib, self.nref)[0] if self.wants_flow else None
+        self.init = self.pred = None
+        self.preds = []
+        return self
+
+    def _draw(self, k, like):
+        """The initial noise of window k's NEW frames: injected, else the unit's seeded INIT stream, else the global generator."""
+        if self.a["init_noises"] is not None:
+            return self.a["init_noises"][k].to(device=self.dev, dtype=torch.float32)
+        if self.seed is not None:
+            return ops.randn(like.shape, self.seed, stream_id(INIT, self.unit, k), device=self.dev)
+        return torch.randn(like.shape, device=self.dev, dtype=torch.float32)
+
+    def window(self, k):
+        a, conds = self.a, self.conds
+        R = self.refs[k - 1] if k else 0
+        new = self._draw(k, conds[k])
+        self.init = torch.cat([self.init[:, -R:], new], dim=1) if k else new   # overlap re-uses the INITIAL noise (:139)
+        start, known = self.plan.window(k, R, self.init)
+        kw = dict(self.text, latent=start, img_cond=torch.cat([conds[k - 1][:, -R:], conds[k]], dim=1) if k else conds[0],
+                  text_cfg=a["text_cfg"], img_cfg=a["video_cfg"], **_seeded(self.seed, self.unit), **known)
+        if self.seed is not None and (k or self.number_first):
+            kw["window"] = k
+        if k:
+            kw.update(latent_ref=self.pred[:, -R:], noise_correct_step=0.5)
+            if a["flows_per_window"] is not None:
+                kw["flows"] = a["flows_per_window"][k - 1]
+            elif self.wants_flow:   # ref_images = the last R frames before this window, query_images = its new frames (:141-147)
+                kw["ref_images"], kw["query_images"] = torch.cat(self.frame_chunks[:k], dim=1)[:, -R:], self.frame_chunks[k]
+        return kw
+
+    def receive(self, k, out):
+        self.pred = out["latent"]
+        self.preds.append(self.pred[:, self.refs[k - 1]:] if k else self.pred)
+
+    def finish(self):
+        latent = torch.cat(self.preds, dim=1)
+        image = self.plan.finish(self.model.decode_latent_to_image(latent), self.frames)
+        if self.keys is None:
+            if self.stab is not None:
+                image = _stabilize(self.source, image, self.stab, self.stab_flows, self.plan.mask_img)
+            return image, latent, self.est
+        # the frames between the keys are filled along the source's flow; with a mask each of them is composited against the input with its
+        # own mask exactly as the key frames were; the filter runs once, on the full-rate result.  The key frames stay bit for bit unless
+        # it runs.  ``latent`` stays the key frames'.
+        from .keyfill import keyframe_fill
+        source, keys = self.source, self.keys
+        fill = keyframe_fill(source, image, keys, flows=self.fill_flows, **{k: self.kf[k] for k in KEYFRAME_KEYS[1:] if k in self.kf})
+        image = fill["frames"]
+        if self.full_mask is not None:
+            rows = torch.tensor([t for t in range(source.shape[1]) if t not in keys], dtype=torch.long, device=image.device)
+            img = image[0].index_select(0, rows).to(torch.float32).contiguous()
+            orig = source[0].to(device=img.device, dtype=torch.float32).index_select(0, rows).contiguous()
+            img = ops.composite(img, orig, self.full_mask.index_select(0, rows).contiguous(), out=img)
+            image[0].index_copy_(0, rows, img.to(image.dtype))
+        if self.stab is not None:
+            image = _stabilize(source, image, self.stab, self.stab_flows, self.full_mask)
+        return image, latent, dict(self.est or {}, keys=list(keys), confidence=fill["confidence"])
 
 
 def _result(image, latent, est, return_latent, return_mask):
@@ -480,79 +550,13 @@ def edit_video(model, inf_pipe, frames, text_cond, text_uncond, text_cfg=7.5, vi
     ``stabilize`` runs once, on the full-rate result.  ``return_latent`` returns the key frames' latent; ``return_mask`` a dict that also
     holds ``keys`` and ``confidence`` [T,H,W] (1 on the key frames).  Not with ``mask="auto"``.  Untuned starting values, as the filter's.
     Without ``keyframes`` nothing of this runs."""
-    check_edit_args(frames.shape, mask, strength, mask_mode, auto_mask, mask_key, mask_flows, mask_track, stabilize, stabilize_flows, mask_shape,
-                    keyframes, key_flows)
-    dev = model.unet.device
-    est = None
-    kf = _keyframe_params(keyframes)
-    if kf is not None:   # before the first window: a missing flow source raises before anything is sampled
-        named = dict(mask=mask, mask_key=mask_key, mask_flows=mask_flows, mask_track=mask_track, stabilize=stabilize, stabilize_flows=stabilize_flows,
-                     mask_shape=mask_shape, key_flows=key_flows, cond=cond, enc_noise=enc_noise)
-        prep = _keyframe_prepare(inf_pipe, frames, kf, named, flow_estimator, dev)
-        if prep is not None:
-            changed, state = prep
-            sub = dict(dict(cond=cond, enc_noise=enc_noise, mask=mask), **changed)
-            image, latent = edit_video(model, inf_pipe, sub.pop("frames"), text_cond, text_uncond, text_cfg, video_cfg, frames_in_batch, num_ref_frames,
-                                       init_noises=init_noises, flows_per_window=flows_per_window, return_latent=True, seed=seed, unit=unit,
-                                       strength=strength, mask_mode=mask_mode, mask_shape=mask_shape, **sub)
-            image, est = _keyframe_finish(state, frames, image, dev)
-            return _result(image, latent, est, return_latent, return_mask)
-    stab, sflows = _stabilize_params(stabilize), None
-    if stab is not None:   # before the first window: a missing flow source raises before anything is sampled
-        sflows, computed = _stabilize_flows(inf_pipe, frames, stab, stabilize_flows, mask_flows, flow_estimator)
-        if computed and mask_key is not None and mask_flows is None:
-            mask_flows = sflows
-    if mask_key is not None:
-        est = _track_mask(inf_pipe, frames, mask, mask_key, mask_flows, flow_estimator, mask_track, dev)
-        mask = est["mask"]
-    z = None
-    if cond is None:
-        z = model.encode_image_to_latent(frames, enc_noise, **_seeded(seed, unit))
-        cond = z / model.scale_factor
-    if isinstance(mask, str):   # "auto" (check_edit_args)
-        est = _estimate_mask(model, inf_pipe, z, cond, text_cond, text_uncond, frames_in_batch, auto_mask, seed, unit)
-        mask = est["mask"]
-    conds, refs = split_batch(cond, frames_in_batch, num_ref_frames)
-    plan = _EditPlan(model, inf_pipe, frames, cond, mask, strength, mask_mode, frames_in_batch, num_ref_frames, z=z, mask_shape=mask_shape)
-    est = _with_shape(est, plan)
-    frame_chunks, _ = split_batch(frames, frames_in_batch, num_ref_frames)
-    rng = _seeded(seed, unit)
-    wants_flow = hasattr(inf_pipe, "obtain_flow_batched")
-    if wants_flow and flows_per_window is None and getattr(inf_pipe, "flow_estimator", None) is None and len(conds) > 1:
-        raise RuntimeError("optical-flow pipeline without a flow source: pass flows_per_window= or build the pipe with flow_estimator=")
-
-    def draw(k, like):
-        if init_noises is not None:
-            return init_noises[k].to(device=dev, dtype=torch.float32)
-        if seed is not None:
-            return ops.randn(like.shape, seed, stream_id(INIT, unit, k), device=dev)
-        return torch.randn(like.shape, device=dev, dtype=torch.float32)
-
-    init = draw(0, conds[0])
-    start, known = plan.window(0, 0, init)
-    pred = inf_pipe(latent=start, text_cond=text_cond, text_uncond=text_uncond, img_cond=conds[0],
-                    text_cfg=text_cfg, img_cfg=video_cfg, **rng, **known)["latent"]
-    preds = [pred]
-    for k, (prev_cond, cond_k, R) in enumerate(zip(conds[:-1], conds[1:], refs)):
-        init = torch.cat([init[:, -R:], draw(k + 1, cond_k)], dim=1)  # overlap re-uses the INITIAL noise (:139)
-        cond_k = torch.cat([prev_cond[:, -R:], cond_k], dim=1)
-        kw = dict(rng, window=k + 1) if rng else {}
-        if flows_per_window is not None:
-            kw["flows"] = flows_per_window[k]
-        elif wants_flow:
-            prev_frames = torch.cat(frame_chunks[:k + 1], dim=1)
-            kw["ref_images"], kw["query_images"] = prev_frames[:, -R:], frame_chunks[k + 1]
-        start, known = plan.window(k + 1, R, init)
-        kw.update(known)
-        pred = inf_pipe.second_clip_forward(latent=start, text_cond=text_cond, text_uncond=text_uncond, img_cond=cond_k,
-                                            latent_ref=pred[:, -R:], noise_correct_step=0.5, text_cfg=text_cfg,
-                                            img_cfg=video_cfg, **kw)["latent"]
-        preds.append(pred[:, R:])
-    latent = torch.cat(preds, dim=1)
-    image = plan.finish(model.decode_latent_to_image(latent), frames)
-    if stab is not None:
-        image = _stabilize(frames, image, stab, sflows, plan.mask_img)
-    return _result(image, latent, est, return_latent, return_mask)
+    args = {k: v for k, v in locals().items() if k in UNIT_KEYS}
+    _check_unit(frames.shape, args)
+    u = _EditUnit(model, inf_pipe, frames, text_cond, text_uncond, frames_in_batch, num_ref_frames, seed, unit, flow_estimator, args).prepare()
+    u.receive(0, inf_pipe(**u.window(0)))
+    for k in range(1, u.windows):
+        u.receive(k, inf_pipe.second_clip_forward(**u.window(k)))
+    return _result(*u.finish(), return_latent, return_mask)
 
 
 @torch.no_grad()
@@ -586,120 +590,29 @@ def edit_videos(model, inf_pipe, units, frames_in_batch=16, num_ref_frames=4, re
     if len(units) == 0:
         return []
     for u in units:
-        check_edit_args(u["frames"].shape, u.get("mask"), u.get("strength", 1.0), u.get("mask_mode", "max"), u.get("auto_mask"),
-                        u.get("mask_key"), u.get("mask_flows"), u.get("mask_track"), u.get("stabilize"), u.get("stabilize_flows"),
-                        u.get("mask_shape"), u.get("keyframes"), u.get("key_flows"))
+        _check_unit(u["frames"].shape, u)
     if len({_start_time(inf_pipe, u.get("strength", 1.0)) for u in units}) > 1:
         raise ValueError("edit_videos: the units of one call must share the number of executed steps (strength); edit the others separately")
-    wants_flow = hasattr(inf_pipe, "obtain_flow_batched")
     ids = [u.get("unit", j) for j, u in enumerate(units)]
     if len(units) == 1:
-        keys = ("text_cfg", "video_cfg", "init_noises", "enc_noise", "cond", "flows_per_window", "mask", "strength", "mask_mode", "auto_mask",
-                "mask_key", "mask_flows", "mask_track", "stabilize", "stabilize_flows", "mask_shape", "keyframes", "key_flows")
+        u = units[0]
         more = {"return_mask": True} if return_mask else {}   # (a plain call carries no new keyword)
         if flow_estimator is not None:
             more["flow_estimator"] = flow_estimator
         return [edit_video(model, inf_pipe, u["frames"], u["text_cond"], u["text_uncond"], frames_in_batch=frames_in_batch,
                            num_ref_frames=num_ref_frames, return_latent=return_latent, seed=seed, unit=ids[0], **more,
-                           **{k: u[k] for k in keys if k in u}) for u in units]
-    dev = model.unet.device
-    if any(_keyframe_params(u.get("keyframes")) is not None for u in units):
-        # key-frame units: each is prepared alone (its flows, its tracked mask), the SUB-VIDEOS of all units stack, each is filled alone
-        subs, states = [], []
-        for u, uid in zip(units, ids):
-            kf = _keyframe_params(u.get("keyframes"))
-            prep = None if kf is None else _keyframe_prepare(inf_pipe, u["frames"], kf, u, flow_estimator, dev)
-            if prep is None:
-                subs.append(dict({k: v for k, v in u.items() if k not in ("keyframes", "key_flows")}, unit=uid))
-            else:
-                subs.append(dict({k: v for k, v in u.items() if k not in _FULL_RATE_ONLY}, unit=uid, **prep[0]))
-            states.append(None if prep is None else prep[1])
-        got = edit_videos(model, inf_pipe, subs, frames_in_batch, num_ref_frames, return_latent=True, seed=seed, max_clips=max_clips,
-                          return_mask=True, flow_estimator=flow_estimator)
-        outs = []
-        for u, state, (image, latent, est) in zip(units, states, got):
-            if state is not None:
-                image, est = _keyframe_finish(state, u["frames"], image, dev)
-            outs.append(_result(image, latent, est, return_latent, return_mask))
-        return outs
-    cap ={} if max_clips is None else {"max_clips": max_clips}   # (a pipe without the parameter keeps working with the default)
-    shape = tuple(units[0]["frames"].shape)
-    st = []
-    for u, uid in zip(units, ids):
-        if tuple(u["frames"].shape) != shape:
-            raise ValueError("edit_videos: all units must share [1,T,3,H,W]")
-        cond, z = u.get("cond"), None
-        if cond is None:
-            z = model.encode_image_to_latent(u["frames"], u.get("enc_noise"), **_seeded(seed, uid))
-            cond = z / model.scale_factor
-        conds, refs = split_batch(cond, frames_in_batch, num_ref_frames)
-        mask, est = u.get("mask"), None
-        stab, sflows, mask_flows = _stabilize_params(u.get("stabilize")), None, u.get("mask_flows")
-        if stab is not None:
-            sflows, computed = _stabilize_flows(inf_pipe, u["frames"], stab, u.get("stabilize_flows"), mask_flows, flow_estimator)
-            if computed and u.get("mask_key") is not None and mask_flows is None:
-                mask_flows = sflows
-        if u.get("mask_key") is not None:   # tracked here, alone, before the first stacked window of any unit
-            est = _track_mask(inf_pipe, u["frames"], mask, u["mask_key"], mask_flows, flow_estimator, u.get("mask_track"), dev)
-            mask = est["mask"]
-        if isinstance(mask, str):   # "auto": estimated here, alone, before the first stacked window of any unit
-            est = _estimate_mask(model, inf_pipe, z, cond, u["text_cond"], u["text_uncond"], frames_in_batch, u.get("auto_mask"), seed, uid)
-            mask = est["mask"]
-        plan = _EditPlan(model, inf_pipe, u["frames"], cond, mask, u.get("strength", 1.0), u.get("mask_mode", "max"),
-                         frames_in_batch, num_ref_frames, z=z, mask_shape=u.get("mask_shape"))
-        est = _with_shape(est, plan)
-        if wants_flow and u.get("flows_per_window") is None and getattr(inf_pipe, "flow_estimator", None) is None and len(conds) > 1:
-            raise RuntimeError("optical-flow pipeline without a flow source: pass flows_per_window= or build the pipe with flow_estimator=")
-        st.append(dict(u=u, unit=uid, conds=conds, refs=refs, preds=[], init=None, pred=None, plan=plan, est=est, stab=stab, sflows=sflows,
-                       frame_chunks=split_batch(u["frames"], frames_in_batch, num_ref_frames)[0] if wants_flow else None))
-
-    def draw(s, k, like):
-        noises = s["u"].get("init_noises")
-        if noises is not None:
-            return noises[k].to(device=dev, dtype=torch.float32)
-        if seed is not None:
-            return ops.randn(like.shape, seed, stream_id(INIT, s["unit"], k), device=dev)
-        return torch.randn(like.shape, device=dev, dtype=torch.float32)
-
-    def common(s, window):
-        u = s["u"]
-        kw = dict(text_cond=u["text_cond"], text_uncond=u["text_uncond"], text_cfg=u.get("text_cfg", 7.5), img_cfg=u.get("video_cfg", 1.8))
-        if seed is not None:
-            kw.update(seed=seed, unit=s["unit"], window=window)
-        return kw
-
-    calls = []
-    for s in st:
-        s["init"] = draw(s, 0, s["conds"][0])
-        start, known = s["plan"].window(0, 0, s["init"])
-        calls.append(dict(common(s, 0), latent=start, img_cond=s["conds"][0], **known))
-    for s, r in zip(st, inf_pipe.run_stacked(calls, **cap)):
-        s["pred"] = r["latent"]
-        s["preds"].append(s["pred"])
-    for k, R in enumerate(st[0]["refs"]):
-        calls = []
-        for s in st:
-            s["init"] = torch.cat([s["init"][:, -R:], draw(s, k + 1, s["conds"][k + 1])], dim=1)  # overlap re-uses the INITIAL noise (:139)
-            cond_k = torch.cat([s["conds"][k][:, -R:], s["conds"][k + 1]], dim=1)
-            start, known = s["plan"].window(k + 1, R, s["init"])
-            call = dict(common(s, k + 1), latent=start, img_cond=cond_k, latent_ref=s["pred"][:, -R:], noise_correct_step=0.5, **known)
-            if s["u"].get("flows_per_window") is not None:
-                call["flows"] = s["u"]["flows_per_window"][k]
-            elif wants_flow:   # ref_images = the last R frames before this window, query_images = its new frames (:141-147)
-                prev_frames = torch.cat(s["frame_chunks"][:k + 1], dim=1)
-                call["ref_images"], call["query_images"] = prev_frames[:, -R:], s["frame_chunks"][k + 1]
-            calls.append(call)
-        for s, r in zip(st, inf_pipe.run_stacked(calls, **cap)):
-            s["pred"] = r["latent"]
-            s["preds"].append(s["pred"][:, R:])
-    outs = []
-    for s in st:
-        latent = torch.cat(s["preds"], dim=1)
-        image = s["plan"].finish(model.decode_latent_to_image(latent), s["u"]["frames"])
-        if s["stab"] is not None:   # each unit alone, after the stacked windows
-            image = _stabilize(s["u"]["frames"], image, s["stab"], s["sflows"], s["plan"].mask_img)
-        outs.append(_result(image, latent, s["est"], return_latent, return_mask))
-    return outs
+                           **{k: u[k] for k in UNIT_KEYS if k in u})]
+    st = [_EditUnit(model, inf_pipe, u["frames"], u["text_cond"], u["text_uncond"], frames_in_batch, num_ref_frames, seed, uid, flow_estimator,
+                    {k: u[k] for k in UNIT_KEYS if k in u}, number_first_window=True) for u, uid in zip(units, ids)]
+    if len({s.shape for s in st}) > 1:   # (of a key-frame unit: its sub-video of key frames, which is what stacks)
+        raise ValueError("edit_videos: all units must share [1,T,3,H,W]")
+    cap = {} if max_clips is None else {"max_clips": max_clips}   # (a pipe without the parameter keeps working with the default)
+    for s in st:   # each alone, before the first stacked window of any unit
+        s.prepare()
+    for k in range(st[0].windows):
+        for s, r in zip(st, inf_pipe.run_stacked([s.window(k) for s in st], **cap)):
+            s.receive(k, r)
+    return [_result(*s.finish(), return_latent, return_mask) for s in st]   # each alone, after the stacked windows
 
 
 def build_parser():
@@ -936,14 +849,32 @@ def want_pixel_scores(args):
     return bool(getattr(args, "score_pixels", False) or getattr(args, "score_warp", False))
 
 
-def write_scores(path, records, rank=0, world=1):
-    """The records of this rank, sorted by unit id (with several ranks each writes its own FILE.rankR.json)."""
-    import json
+def unit_record(args, unit, frames, edited, scorer=None, texts=None, est=None, drawn=None, flow_estimator=None):
+    """A unit's --score-out record, assembled from its parts: the CLIP scores (``scorer``, with ``texts()`` = the source and the edit
+    prompt), the pixel scores (the region: the unit's image-resolution mask - shaped, tracked or estimated if the run made one, ``est``,
+    else as ``drawn``) and the key-frame fields."""
+    rec = {"unit": int(unit)}
+    if scorer is not None:   # the edited frames are still on the device
+        rec.update(score_record(scorer, unit, frames, edited, *texts()))
+    if want_pixel_scores(args):
+        rec.update(pixel_record(args, frames, edited, mask_region(est, drawn), flow_estimator))
+    rec.update(keyframe_record(args, est))
+    return rec
+
+
+def _rank_path(path, rank, world):
+    """This rank's output path (with several ranks each writes its own FILE.rankR.ext), its directory created."""
     if world > 1:
         root, ext = os.path.splitext(path)
         path = f"{root}.rank{rank}{ext}"
     os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
-    with open(path, "w") as f:
+    return path
+
+
+def write_scores(path, records, rank=0, world=1):
+    """The records of this rank, sorted by unit id (with several ranks each writes its own FILE.rankR.json)."""
+    import json
+    with open(_rank_path(path, rank, world), "w") as f:
         json.dump(sorted(records, key=lambda r: r["unit"]), f, indent=1)
 
 
@@ -1050,25 +981,13 @@ def write_masks(path, records, rank=0, world=1):
     --mask-feather) writes every unit's "shaped" and "support" [T,H,W] next to whatever its source returned."""
     records = {u: est for u, est in records.items() if est is not None and set(est) - {"keys", "confidence"}}   # (a unit the mask file does not name has none)
     if any("shaped" in est for est in records.values()):   # --mask-grow / --mask-feather: what the source gave, and the two shaped masks
-        if world > 1:
-            root, ext = os.path.splitext(path)
-            path = f"{root}.rank{rank}{ext}"
-        os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
         keys = ("mask", "valid", "mask_latent", "soft", "shaped", "support")
-        torch.save({int(u): {k: (est[k] if k == "valid" else est[k][0]).cpu() for k in keys if k in est} for u, est in sorted(records.items())}, path)
-        return
-    if any("valid" in est for est in records.values()):
-        if world > 1:
-            root, ext = os.path.splitext(path)
-            path = f"{root}.rank{rank}{ext}"
-        os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
-        torch.save({int(u): {"mask": est["mask"][0].cpu(), "valid": est["valid"].cpu()} for u, est in sorted(records.items())}, path)
-        return
-    if world > 1:
-        root, ext = os.path.splitext(path)
-        path = f"{root}.rank{rank}{ext}"
-    os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
-    torch.save({int(u): {k: est[k][0].cpu() for k in ("mask_latent", "soft")} for u, est in sorted(records.items())}, path)
+    elif any("valid" in est for est in records.values()):
+        keys = ("mask", "valid")
+    else:
+        keys = ("mask_latent", "soft")
+    torch.save({int(u): {k: (est[k] if k == "valid" else est[k][0]).cpu() for k in keys if k in est or "shaped" not in keys}
+                for u, est in sorted(records.items())}, _rank_path(path, rank, world))
 
 
 def synthetic_mask(n, H, W):
@@ -1088,6 +1007,22 @@ def optical_flow_pipe_kwargs(args):
     return {"raft_state_dict": synth.synth_raft_state_dict(shapes.raft_shapes())}
 
 
+def cli_options(args, device, data=None):
+    """What the flags add to a run -> (per, more, want_masks, estimator): ``per`` = what every unit gets - ``per["all"]`` (--auto-mask,
+    --stabilize, --key-stride) whatever its mask, ``per["masked"](has_mask)`` (--mask-key with a drawn mask, the shaping flags with a
+    drawn or an estimated one) according to it; ``more`` = the keywords of the drivers (the flow estimator, when a feature follows the
+    source's flows); ``want_masks`` = ``return_mask`` when something reads the units' masks, else nothing: a plain run carries no new
+    keyword.  ``data``: the --units file, whose own "mask" entry --auto-mask refuses."""
+    auto, track, shape = auto_mask_unit(args, data), mask_track_unit(args), mask_shape_unit(args)
+    stab, keyf = stabilize_unit(args), keyframe_unit(args)
+    estimator = build_flow_estimator(args, device)
+    per = dict(all=dict(**auto, **stab, **keyf), masked=lambda has_mask: dict(**(track if has_mask else {}), **(shape if has_mask or auto else {})))
+    more = {"flow_estimator": estimator} if track or stab or keyf else {}
+    want_masks = {"return_mask": True} if ((auto or track or shape) and (getattr(args, "mask_out", None) or getattr(args, "score_pixels", False))) \
+        or (keyf and getattr(args, "score_out", None)) else {}
+    return per, more, want_masks, estimator
+
+
 def run_dataset(args, model, pipe, rank=0, world=1, scorer=None):
     """The reference's main loop (insv2v_run_loveu_tgve.py:83-170): every (video, cfg, size) x 4 prompt kinds is one
     independent unit; units are dealt round-robin to ranks, each rank writes its own result files.  With ``--seed`` a unit's id is
@@ -1104,13 +1039,8 @@ def run_dataset(args, model, pipe, rank=0, world=1, scorer=None):
     seed = getattr(args, "seed", None)
     kinds = ("style", "object", "background", "multiple")
     records = []
-    auto = auto_mask_unit(args)
-    track, drawn = mask_track_unit(args), load_mask_file(args)   # drawn masks are named by video here
-    estimator = build_flow_estimator(args, model.unet.device)
-    stab, shape, keyf = stabilize_unit(args), mask_shape_unit(args), keyframe_unit(args)
-    more = {"flow_estimator": estimator} if track or stab or keyf else {}
-    want_masks = {"return_mask": True} if ((auto or track or shape) and (getattr(args, "mask_out", None) or getattr(args, "score_pixels", False))) \
-        or (keyf and getattr(args, "score_out", None)) else {}   # (a plain run carries no new keyword)
+    drawn = load_mask_file(args)   # drawn masks are named by video here
+    per, more, want_masks, estimator = cli_options(args, model.unet.device)
     masks = {}
     for ci, (video_id, text_cfg, video_cfg, num_frames, image_size) in enumerate(combos):
         if ci % world != rank:
@@ -1133,10 +1063,9 @@ def run_dataset(args, model, pipe, rank=0, world=1, scorer=None):
                 continue
             todo.append((gif_path, image_dir, dict(frames=frames, text_cond=model.encode_text([prompt]), text_uncond=text_uncond,
                                                    text_cfg=text_cfg, video_cfg=video_cfg, cond=cond, unit=4 * ci + kinds.index(key),
-                                                   strength=getattr(args, "strength", 1.0), **auto, **stab, **keyf,
-                                                   **(shape if auto or batch["video_name"] in drawn else {}),
-                                                   **(dict(mask=drawn[batch["video_name"]], mask_mode=getattr(args, "mask_mode", "max"),
-                                                           **track) if batch["video_name"] in drawn else {})), prompt))
+                                                   strength=getattr(args, "strength", 1.0), **per["all"], **per["masked"](batch["video_name"] in drawn),
+                                                   **(dict(mask=drawn[batch["video_name"]], mask_mode=getattr(args, "mask_mode", "max"))
+                                                      if batch["video_name"] in drawn else {})), prompt))
         # the four prompts of a video share the conditioning latent and the window plan: one stacked launch chain per window (B = 12)
         if getattr(args, "no_stack", False):
             edits = [edit_videos(model, pipe, [u], seed=seed, **want_masks, **more)[0] for _, _, u, _ in todo]
@@ -1145,14 +1074,8 @@ def run_dataset(args, model, pipe, rank=0, world=1, scorer=None):
         for (gif_path, image_dir, u, prompt), edited in zip(todo, edits):
             if want_masks:
                 edited, masks[u["unit"]] = edited
-            rec = {"unit": int(u["unit"])}
-            if scorer is not None:   # the edited frames are still on the device
-                rec.update(score_record(scorer, u["unit"], frames, edited, batch["original"], prompt))
-            if want_pixel_scores(args):   # the region: the unit's image-resolution mask - tracked or estimated if the run made one, else as drawn
-                est = masks.get(u["unit"])
-                rec.update(pixel_record(args, frames, edited, mask_region(est, u.get("mask")), estimator))
-            rec.update(keyframe_record(args, masks.get(u["unit"])))
-            records.append(rec)
+            records.append(unit_record(args, u["unit"], frames, edited, scorer, lambda: (batch["original"], prompt), masks.get(u["unit"]),
+                                       u.get("mask"), estimator))
             save_tensor_to_gif(torch.cat([frames.float().cpu(), edited.float().cpu()], dim=4), gif_path, fps=5)
             save_tensor_to_images(edited.float().cpu(), image_dir)
     if scorer is not None or want_pixel_scores(args):
@@ -1225,24 +1148,19 @@ def main(argv=None):
     n = data["frames"].shape[0]
     flows = torch.load(args.flows, map_location="cpu") if args.flows else None
     item_shape = tuple(data["frames"].shape[1:])  # a rank without units still takes part in the all_gather
-    auto = auto_mask_unit(args, data)   # (refuses --auto-mask next to a "mask" entry of the file)
-    track, drawn = mask_track_unit(args), load_mask_file(args)   # drawn masks are named by unit here
+    drawn = load_mask_file(args)   # drawn masks are named by unit here
     image_mask = load_mask_image(args, data["frames"].shape[-1], data["frames"].shape[-2])   # every unit gets it
     if (drawn or image_mask is not None) and data.get("mask") is not None:
         raise SystemExit("--mask-file / --mask-image next to the \"mask\" entry of the --units file are two masks: pass one")
-    if track and not drawn and image_mask is None and data.get("mask") is None:
+    if args.mask_key is not None and not drawn and image_mask is None and data.get("mask") is None:
         raise SystemExit("--mask-key needs a mask to track: --mask-file FILE.pt, the \"mask\" entry of a --units file, or --synthetic-mask")
-    estimator = build_flow_estimator(args, f"cuda:{local}")
-    stab, shape, keyf = stabilize_unit(args), mask_shape_unit(args), keyframe_unit(args)
-    more = {"flow_estimator": estimator} if track or stab or keyf else {}
-    want_masks = {"return_mask": True} if ((auto or track or shape) and (args.mask_out or args.score_pixels)) or (keyf and args.score_out) else {}
+    per, more, want_masks, estimator = cli_options(args, f"cuda:{local}", data)   # (refuses --auto-mask next to a "mask" entry of the file)
     est_masks = {}
     masks = data.get("mask")   # optional [n,T,H,W] / [n,1,H,W]
 
     def edit(i):
         m = masks[i:i + 1] if masks is not None else drawn.get(i, image_mask)
-        return dict(dict(mask=m, strength=args.strength, mask_mode=args.mask_mode), **auto, **stab, **keyf, **(track if m is not None else {}),
-                    **(shape if m is not None or auto else {}))
+        return dict(dict(mask=m, strength=args.strength, mask_mode=args.mask_mode), **per["all"], **per["masked"](m is not None))
     scorer = build_scorer(args, f"cuda:{local}", tok)
     records = []
     outs = []
@@ -1269,14 +1187,8 @@ def main(argv=None):
                 est_masks[ci * n + i] = est
             local_out = [img for img, _ in local_out]
         for i, edited in zip(mine, local_out if scorer is not None or want_pixel_scores(args) else []):
-            rec = {"unit": ci * n + i}
-            if scorer is not None:
-                rec.update(score_record(scorer, ci * n + i, data["frames"][i:i + 1], edited, *_score_texts(data, i, scorer)))
-            if want_pixel_scores(args):   # the region: the unit's image-resolution mask - tracked or estimated if the run made one, else as drawn
-                est = est_masks.get(ci * n + i)
-                rec.update(pixel_record(args, data["frames"][i:i + 1], edited, mask_region(est, edit(i)["mask"]), estimator))
-            rec.update(keyframe_record(args, est_masks.get(ci * n + i)))
-            records.append(rec)
+            records.append(unit_record(args, ci * n + i, data["frames"][i:i + 1], edited, scorer, lambda: _score_texts(data, i, scorer),
+                                       est_masks.get(ci * n + i), edit(i)["mask"], estimator))
         local_out = torch.cat(local_out, 0).half() if local_out else torch.zeros((0, *item_shape), device=model.unet.device).half()
         outs.append(gather_frames(local_out, n, item_shape=item_shape))
     if scorer is not None or want_pixel_scores(args):

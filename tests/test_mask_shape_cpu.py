@@ -520,37 +520,7 @@ def test_write_masks_holds_the_shaped_mask(tmp_path):
 
 
 # ------------------------------------------------------------------------------------------------------------------ 7. drivers on the host
-class _Model:
-    scale_factor = 0.5
-
-    class unet:
-        device = torch.device("cpu")
-
-    def encode_image_to_latent(self, frames, noise=None, **kw):
-        return frames[:, :, :1].repeat(1, 1, 4, 1, 1)[..., ::8, ::8].contiguous()
-
-    def decode_latent_to_image(self, latent):
-        return latent[:, :, :3].repeat_interleave(8, -1).repeat_interleave(8, -2)
-
-
-class _RecordingPipe:
-    """Records the keywords of every call the drivers make."""
-    num_ddim_steps = 4
-
-    def __init__(self):
-        self.calls = []
-
-    def __call__(self, **kw):
-        self.calls.append(("call", sorted(kw)))
-        return {"latent": kw["latent"]}
-
-    def second_clip_forward(self, **kw):
-        self.calls.append(("second", sorted(kw)))
-        return {"latent": kw["latent"]}
-
-    def run_stacked(self, calls, **kw):
-        self.calls.append(("stacked", [sorted(c) for c in calls], sorted(kw)))
-        return [{"latent": c["latent"]} for c in calls]
+from driver_fakes import Model as _Model, RecordingPipe as _RecordingPipe   # noqa: E402
 
 
 def test_a_call_without_mask_shape_is_what_it_was(monkeypatch):
