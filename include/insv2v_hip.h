@@ -1183,6 +1183,72 @@ typedef struct insv2v_mask_shape_desc {
 int64_t insv2v_mask_shape_workspace_bytes(int32_t T, int32_t H, int32_t W);
 int insv2v_mask_shape(const insv2v_mask_shape_desc* d, insv2v_stream_t stream);
 
+/*
+ * ---- editing a region at full resolution (additions to ABI 15: no existing struct or entry changes) ------------------------------------------
+ * The box around a mask is resampled to the model's working size, edited there, and what the edit changed is resampled back and laid
+ * over the untouched full-resolution source (csrc/region.hip; tests/region_ref.py restates the definition in
+ * float64).  All operands are fp32; views have element strides and contiguous rows, so a crop of a larger tensor is a valid operand.
+ *
+ * RESAMPLING is the separable antialiased resampling of torch.nn.functional.interpolate(antialias=True, align_corners=False) applied
+ * to the CROP.  Per axis, with n_in source and n_out destination samples: scale = n_in / n_out, s = max(scale, 1); for destination
+ * index i: c = scale (i + 0.5), xmin = max(int(c - support s + 0.5), 0), xsize = min(int(c + support s + 0.5), n_in) - xmin, weights
+ * f((j + xmin - c + 0.5) / s) for j < xsize, divided by their sum.  INSV2V_REGION_BICUBIC: the cubic convolution with A = -0.5,
+ * support 2; INSV2V_REGION_BILINEAR: the triangle, support 1.  The taps are clipped at the edges of the BOX, not of the frame.  c and the
+ * tap range are formed in double, the weights in fp32 and normalised by their sum in tap order; the horizontal pass comes first, every
+ * output is an fp32 fma chain in tap order.  With n_in == n_out the weights are exactly 0, 1, 0, 0: an equal-size box is copied bit
+ * for bit.  One launch for all frames and channels, no intermediate image in HBM, no atomics: two calls give the same bits.
+ * Every entry returns INSV2V_EINVAL before any launch, and leaves its outputs untouched, for: a NULL descriptor or required pointer; a
+ * size that is not positive (or a side above 2^24, a box or working height above 16 * 65535, or more than 65535 planes n * C); a box that is empty or not inside the frame; a
+ * per-axis ratio box / working size outside [1/8, 8] (what bounds the kernels' LDS staging); an unknown filter or mode; a negative
+ * stride or a row stride below W; an output that overlaps an input.
+ */
+#define INSV2V_REGION_BICUBIC 0
+#define INSV2V_REGION_BILINEAR 1
+#define INSV2V_REGION_RESIDUAL 0
+#define INSV2V_REGION_REPLACE 1
+/* boxes[T + 1][4] int32: per frame of the mask view [T,H,W] (stride_t may be 0: one mask for every frame) and, in entry T, over all
+ * frames, the half-open box (x0, y0, x1, y1) of the pixels with mask > threshold (strict; a NaN is outside); a frame without one gives
+ * (W, H, 0, 0).  The entry initialises boxes itself (two launches); the reduction ends in integer min / max atomics, which commute:
+ * the result is a function of the inputs only.  Also INSV2V_EINVAL: T above 65534, a threshold that is not finite. */
+int insv2v_mask_bbox(const float* mask, int64_t stride_t, int64_t stride_h, int32_t T, int32_t H, int32_t W, float threshold,
+                     int32_t* boxes, insv2v_stream_t stream);
+/* dst[n,C,h,w] = resample(src[n,C, y0:y1, x0:x1] -> (h, w)) with `filter`; clamp != 0: then clamped to [clamp_lo, clamp_hi] (a NaN
+ * stays a NaN).  Also INSV2V_EINVAL: clamp outside {0, 1}, clamp_lo > clamp_hi. */
+typedef struct insv2v_region_resample_desc {
+    const float* src;          /* [n,C,H,W] view */
+    int64_t src_stride_n, src_stride_c, src_stride_h;
+    float* dst;                /* [n,C,h,w] contiguous */
+    int32_t n, C, H, W, h, w;
+    int32_t x0, y0, x1, y1;    /* the box, half-open, inside the frame */
+    int32_t filter, clamp;
+    float clamp_lo, clamp_hi;
+} insv2v_region_resample_desc;
+int insv2v_region_resample(const insv2v_region_resample_desc* d, insv2v_stream_t stream);
+/* The paste.  `out` [n,C,H,W] holds the SOURCE (the caller hands in a clone); only the box is written, and a pixel is read before it is
+ * written, by the same thread.  ramp(x, y) = min(1, (d + 0.5) / blend), d = the distance in pixels to the nearest box edge that is not
+ * also a frame border (1 when blend == 0, or when no such edge exists).  With U(.) the bicubic and V(.) the bilinear resampling of a
+ * working-resolution [h,w] image to the box:
+ *   INSV2V_REGION_RESIDUAL:  out = clip(src + ramp U(edit - down), -1, 1)     the difference is formed in fp32 as the operand is loaded:
+ *                            where edit == down in all of a pixel's taps the added term is exactly 0 and the pixel keeps the source's value
+ *   INSV2V_REGION_REPLACE:   out = clip(src + M (U(edit) - src), -1, 1),  M = ramp clamp(V(mask), 0, 1), M = ramp when mask == NULL;
+ *                            `down` is not read
+ * In both modes a pixel whose added term is exactly 0 (0.f == the term) keeps the source's own bits, also those of a -0, before the clip.
+ * mask [n,h,w] has rows of w and planes of h * w; mask_stride_n is the frame stride (0: one mask for every frame).  Also
+ * INSV2V_EINVAL: down == NULL in residual mode; a blend that is negative or not finite; a mask stride below h * w other than 0. */
+typedef struct insv2v_region_paste_desc {
+    const float* edit;         /* [n,C,h,w] contiguous: the edited working clip */
+    const float* down;         /* [n,C,h,w] contiguous: the working clip the edit started from (residual mode) */
+    const float* mask;         /* [n,h,w] or NULL (replace mode) */
+    int64_t mask_stride_n;
+    float* out;                /* [n,C,H,W] view */
+    int64_t out_stride_n, out_stride_c, out_stride_h;
+    int32_t n, C, H, W, h, w;
+    int32_t x0, y0, x1, y1;
+    int32_t mode;
+    float blend;
+} insv2v_region_paste_desc;
+int insv2v_region_paste(const insv2v_region_paste_desc* d, insv2v_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,6 +16,7 @@ def __getattr__(name):
         "InstructP2PVideoModel": ".model", "create_model": ".model", "unit_test_create_model": ".model",
         "warp_image": ".flow_utils", "resize_flow": ".flow_utils", "split_batch": ".run_loveu_tgve",
         "edit_video": ".run_loveu_tgve", "keyframe_fill": ".keyfill", "key_frames": ".keyfill",
+        "edit_region": ".region", "edit_regions": ".region", "region_plan": ".region",
     }
     if name in table:
         return getattr(importlib.import_module(table[name], __name__), name)

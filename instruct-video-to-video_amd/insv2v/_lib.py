@@ -209,6 +209,24 @@ class MaskShapeDesc(C.Structure):
                 ("T", c_i32), ("H", c_i32), ("W", c_i32), ("threshold", c_f32), ("grow", c_f32), ("feather", c_f32), ("profile", c_i32)]
 
 
+REGION_FILTERS, REGION_MODES = ("bicubic", "bilinear"), ("residual", "replace")   # INSV2V_REGION_BICUBIC / _BILINEAR, _RESIDUAL / _REPLACE in their order
+
+
+class RegionResampleDesc(C.Structure):
+    """insv2v_region_resample_desc (csrc/region.hip)."""
+    _fields_ = [("src", c_p), ("src_stride_n", c_i64), ("src_stride_c", c_i64), ("src_stride_h", c_i64), ("dst", c_p),
+                ("n", c_i32), ("C", c_i32), ("H", c_i32), ("W", c_i32), ("h", c_i32), ("w", c_i32),
+                ("x0", c_i32), ("y0", c_i32), ("x1", c_i32), ("y1", c_i32), ("filter", c_i32), ("clamp", c_i32), ("clamp_lo", c_f32), ("clamp_hi", c_f32)]
+
+
+class RegionPasteDesc(C.Structure):
+    """insv2v_region_paste_desc (csrc/region.hip)."""
+    _fields_ = [("edit", c_p), ("down", c_p), ("mask", c_p), ("mask_stride_n", c_i64), ("out", c_p),
+                ("out_stride_n", c_i64), ("out_stride_c", c_i64), ("out_stride_h", c_i64),
+                ("n", c_i32), ("C", c_i32), ("H", c_i32), ("W", c_i32), ("h", c_i32), ("w", c_i32),
+                ("x0", c_i32), ("y0", c_i32), ("x1", c_i32), ("y1", c_i32), ("mode", c_i32), ("blend", c_f32)]
+
+
 # name -> (restype, argtypes); mirrors include/insv2v_hip.h one to one.
 SIGNATURES = {
     "insv2v_abi_version": (c_i32, []),
@@ -286,6 +304,9 @@ SIGNATURES = {
     "insv2v_mask_shape_plan": (c_i32, [c_f32, c_f32, C.POINTER(MaskShapePlan)]),
     "insv2v_mask_shape_workspace_bytes": (c_i64, [c_i32, c_i32, c_i32]),
     "insv2v_mask_shape": (c_i32, [C.POINTER(MaskShapeDesc), c_p]),
+    "insv2v_mask_bbox": (c_i32, [c_p, c_i64, c_i64, c_i32, c_i32, c_i32, c_f32, c_p, c_p]),
+    "insv2v_region_resample": (c_i32, [C.POINTER(RegionResampleDesc), c_p]),
+    "insv2v_region_paste": (c_i32, [C.POINTER(RegionPasteDesc), c_p]),
 }
 
 _lib = None

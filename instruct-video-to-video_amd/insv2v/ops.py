@@ -1443,3 +1443,83 @@ def mask_shape(mask, *, grow=0.0, feather=0.0, threshold=0.5, profile="smooth", 
     d.T, d.H, d.W, d.threshold, d.grow, d.feather, d.profile = T, H, W, threshold, grow, feather, _lib.MASK_PROFILES.index(profile)
     check(lib.insv2v_mask_shape(_byref(d), _stream()), "insv2v_mask_shape")
     return tuple(out)
+
+
+# ----------------------------------------------------------------------------- editing a region at full resolution (insv2v/region.py)
+def _region_view(t, name):
+    """An fp32 CUDA [n,C,H,W] tensor, any view whose rows are contiguous (a broadcast frame or channel has stride 0)."""
+    _req(t, torch.float32, name)
+    if t.dim() != 4 or (t.shape[3] > 1 and t.stride(3) != 1):
+        raise _lib.HipKernelError(f"{name}: {tuple(t.shape)} (strides {t.stride()}) must be [n,C,H,W] with contiguous rows")
+    return tuple(t.shape)
+
+
+def mask_bbox(mask, *, threshold=0.5, out=None):
+    """insv2v_mask_bbox (tests/region_ref.py is the definition): ``mask`` fp32 [T,H,W], any view with contiguous
+    rows (a [1,H,W] mask expanded to T frames has frame stride 0) -> int32 [T + 1, 4] on the device: per frame and, in the last row,
+    over all frames the half-open box (x0, y0, x1, y1) of ``mask > threshold``; (W, H, 0, 0) where there is none."""
+    lib = _lib.load()
+    _req(mask, torch.float32, "mask_bbox.mask")
+    if mask.dim() != 3 or (mask.shape[2] > 1 and mask.stride(2) != 1):
+        raise _lib.HipKernelError(f"mask_bbox: mask {tuple(mask.shape)} (strides {mask.stride()}) must be [T,H,W] with contiguous rows")
+    T, H, W = mask.shape
+    if out is None:
+        out = torch.empty((T + 1, 4), device=mask.device, dtype=torch.int32)
+    _plain(out, (T + 1, 4), "mask_bbox.out", torch.int32)
+    check(lib.insv2v_mask_bbox(mask.data_ptr() or None, mask.stride(0), mask.stride(1), T, H, W, threshold, out.data_ptr() or None, _stream()),
+          "insv2v_mask_bbox")
+    return out
+
+
+def region_resample(src, box, size, *, mode="bicubic", clamp=None, out=None):
+    """insv2v_region_resample: ``src`` fp32 [n,C,H,W] (any view with contiguous rows), ``box`` (x0, y0, x1, y1) inside the frame,
+    ``size`` (w, h) -> fp32 [n,C,h,w]: the box resampled with the antialiased ``mode`` ("bicubic" / "bilinear") of
+    ``torch.nn.functional.interpolate``, taps clipped at the box; ``clamp=(lo, hi)`` clamps the result."""
+    lib = _lib.load()
+    n, Cn, H, W = _region_view(src, "region_resample.src")
+    if mode not in _lib.REGION_FILTERS:
+        raise ValueError(f"region_resample: mode {mode!r} is neither 'bicubic' nor 'bilinear'")
+    w, h = (int(v) for v in size)
+    if out is None:
+        out = torch.empty((n, Cn, max(h, 0), max(w, 0)), device=src.device, dtype=torch.float32)
+    _plain(out, (n, Cn, h, w), "region_resample.out")
+    d = _lib.RegionResampleDesc()
+    d.src, d.dst = src.data_ptr() or None, out.data_ptr() or None
+    d.src_stride_n, d.src_stride_c, d.src_stride_h = src.stride(0), src.stride(1), src.stride(2)
+    d.n, d.C, d.H, d.W, d.h, d.w = n, Cn, H, W, h, w
+    d.x0, d.y0, d.x1, d.y1 = (int(v) for v in box)
+    d.filter, d.clamp = _lib.REGION_FILTERS.index(mode), int(clamp is not None)
+    d.clamp_lo, d.clamp_hi = clamp if clamp is not None else (0.0, 0.0)
+    check(lib.insv2v_region_resample(_byref(d), _stream()), "insv2v_region_resample")
+    return out
+
+
+def region_paste(out, edit_w, down_src, box, *, mode="residual", blend=8, mask_w=None):
+    """insv2v_region_paste, IN PLACE: ``out`` fp32 [n,C,H,W] (any view with contiguous rows) holds the source; its ``box`` takes the
+    working-resolution edit ``edit_w`` [n,C,h,w]: ``mode="residual"`` adds ``edit_w - down_src`` resampled to the box, ``"replace"``
+    blends the resampled ``edit_w`` in under ``mask_w`` ([n,h,w], or [1,h,w] for every frame, or None: ones), each under the ramp of
+    ``blend`` pixels at the box edges that are not frame borders.  Returns ``out``."""
+    lib = _lib.load()
+    n, Cn, H, W = _region_view(out, "region_paste.out")
+    if mode not in _lib.REGION_MODES:
+        raise ValueError(f"region_paste: mode {mode!r} is neither 'residual' nor 'replace'")
+    _req(edit_w, torch.float32, "region_paste.edit_w")
+    if edit_w.dim() != 4 or tuple(edit_w.shape[:2]) != (n, Cn) or not edit_w.is_contiguous():
+        raise _lib.HipKernelError(f"region_paste: edit_w {tuple(edit_w.shape)} must be a contiguous [{n},{Cn},h,w]")
+    h, w = edit_w.shape[2:]
+    d = _lib.RegionPasteDesc()
+    if mode == "residual":
+        _plain(down_src, (n, Cn, h, w), "region_paste.down_src")
+        d.down = down_src.data_ptr() or None
+    elif mask_w is not None:
+        _req(mask_w, torch.float32, "region_paste.mask_w")
+        if mask_w.dim() != 3 or mask_w.shape[0] not in (1, n) or tuple(mask_w.shape[1:]) != (h, w) or not mask_w.is_contiguous():
+            raise _lib.HipKernelError(f"region_paste: mask_w {tuple(mask_w.shape)} must be a contiguous [{n},{h},{w}] or [1,{h},{w}]")
+        d.mask, d.mask_stride_n = mask_w.data_ptr() or None, (h * w if mask_w.shape[0] == n and n > 1 else 0)
+    d.edit, d.out = edit_w.data_ptr() or None, out.data_ptr() or None
+    d.out_stride_n, d.out_stride_c, d.out_stride_h = out.stride(0), out.stride(1), out.stride(2)
+    d.n, d.C, d.H, d.W, d.h, d.w = n, Cn, H, W, h, w
+    d.x0, d.y0, d.x1, d.y1 = (int(v) for v in box)
+    d.mode, d.blend = _lib.REGION_MODES.index(mode), float(blend)
+    check(lib.insv2v_region_paste(_byref(d), _stream()), "insv2v_region_paste")
+    return out

@@ -713,6 +713,20 @@ def build_parser():
                    help="how much the source may differ between an in-between frame and its key along a trajectory, on [0, 1] data (default 0.1)")
     p.add_argument("--key-no-occlusion", action="store_true", help="with --key-stride: no forward-backward consistency check on the trajectories")
     p.add_argument("--synthetic-tiny", action="store_true", help="with --synthetic: the reduced-width UNet / VAE (and scorer) configurations")
+    p.add_argument("--region", action="store_true",
+                   help="edit a region at full resolution (insv2v/region.py): the frames keep their native size, the box around the mask of "
+                        "--mask-image / --mask-file (else the whole frame) is resampled to --image-size, which is then the WORKING size, "
+                        "edited there and pasted back over the untouched source; scores are taken at the source's resolution; the "
+                        "--region-* values are starting points, untuned")
+    p.add_argument("--region-box", nargs=4, type=int, default=None, metavar=("X0", "Y0", "X1", "Y1"),
+                   help="with --region: the box to edit, in source pixels, half-open (default: the box around the mask; the whole frame "
+                        "without a drawn mask, also with --auto-mask / --mask-key, whose masks exist only at working resolution)")
+    p.add_argument("--region-pad", type=float, default=None, help="with --region: the mask's box grows by F x its longer side (default 0.25)")
+    p.add_argument("--region-mode", type=str, default=None,
+                   help="residual (default): carry what the edit CHANGED up to the source's resolution; replace: blend the resampled edit in under the mask")
+    p.add_argument("--region-blend", type=float, default=None, help="with --region: pixels over which the paste ramps in at the box edges (default 8)")
+    p.add_argument("--region-source", nargs=2, type=int, default=None, metavar=("W", "H"),
+                   help="with --synthetic and --region: the size of the synthetic source frames (default: --image-size)")
     return p
 
 
@@ -810,6 +824,17 @@ def check_args(args):
         raise SystemExit("--score-ckpt / --score-synthetic need --score-out FILE.json for the scores")
     if getattr(args, "synthetic_tiny", False) and not args.synthetic:
         raise SystemExit("--synthetic-tiny needs --synthetic N")
+    if getattr(args, "region", False):
+        from .region import check_region
+        for size in args.image_size:
+            try:
+                check_region(region_unit(args, size)["region"])
+            except ValueError as e:
+                raise SystemExit(f"--region / --region-box / --region-pad / --region-mode / --region-blend (working size --image-size {size}): {e}")
+        if getattr(args, "region_source", None) is not None and (not args.synthetic or min(args.region_source) < 1):
+            raise SystemExit("--region-source W H sets the size of the --synthetic N source frames: it needs --synthetic and two positive numbers")
+    elif any(getattr(args, k, None) is not None for k in ("region_box", "region_pad", "region_mode", "region_blend", "region_source")):
+        raise SystemExit("--region-box / --region-pad / --region-mode / --region-blend / --region-source are parameters of --region")
     return args
 
 
@@ -937,12 +962,39 @@ def mask_shape_unit(args):
     return dict(mask_shape=given) if given else {}
 
 
+def region_unit(args, image_size=None):
+    """What --region adds to every unit (nothing without it): ``region=`` of ``region.edit_region`` with the working size --image-size
+    (``image_size``: that of one combination) and only the values given; the others keep ``check_region``'s defaults.  Without
+    --region-box the box comes from the unit's drawn mask; --auto-mask and --mask-key make their mask inside the working-resolution
+    edit, so they take the whole frame."""
+    if not getattr(args, "region", False):
+        return {}
+    S = args.image_size[0] if image_size is None else image_size
+    r = dict(size=(S, S))
+    if getattr(args, "region_box", None) is not None:
+        r["box"] = tuple(args.region_box)
+    elif getattr(args, "auto_mask", False) or getattr(args, "mask_key", None) is not None:
+        r["box"] = "frame"
+    for k in ("pad", "mode", "blend"):
+        if getattr(args, "region_" + k, None) is not None:
+            r[k] = getattr(args, "region_" + k)
+    return dict(region=r)
+
+
+def region_est(args, est):
+    """The dict the scores read a unit's mask from: with --region the masks a run computed are at WORKING resolution, and the scores are
+    taken at the source's, so only the drawn mask splits them."""
+    if not getattr(args, "region", False) or est is None:
+        return est
+    return {k: v for k, v in est.items() if k not in ("shaped", "support", "mask")}
+
+
 def load_mask_image(args, width, height):
-    """The mask of --mask-image at the frames' size ([1,1,H,W] or [1,T,H,W]; None without it)."""
+    """The mask of --mask-image at the frames' size ([1,1,H,W] or [1,T,H,W]; None without it); ``width=None``: at its native size."""
     if not getattr(args, "mask_image", None):
         return None
     from .video_io import load_mask
-    return load_mask(args.mask_image, (width, height))
+    return load_mask(args.mask_image, None if width is None else (width, height))
 
 
 def mask_region(est, drawn):
@@ -1042,17 +1094,19 @@ def run_dataset(args, model, pipe, rank=0, world=1, scorer=None):
     drawn = load_mask_file(args)   # drawn masks are named by video here
     per, more, want_masks, estimator = cli_options(args, model.unet.device)
     masks = {}
+    on_region = bool(region_unit(args))   # the frames and the mask image keep their native size; image_size is the working size
     for ci, (video_id, text_cfg, video_cfg, num_frames, image_size) in enumerate(combos):
         if ci % world != rank:
             continue
-        batch = LoveuTgveVideoDataset(root_dir=args.data_dir, image_size=(image_size, image_size))[video_id]
+        batch = LoveuTgveVideoDataset(root_dir=args.data_dir, image_size=None if on_region else (image_size, image_size))[video_id]
         n = len(batch["frames"])
         skip = n // num_frames if n > num_frames else 1
         frames = batch["frames"][::skip].to(model.unet.device)[None]
         text_uncond = model.encode_text([""])
         if getattr(args, "mask_image", None):   # every video gets the image's mask, at this combination's frame size
-            drawn = {batch["video_name"]: load_mask_image(args, image_size, image_size)}
-        cond = model.encode_image_to_latent(frames, **_seeded(seed, 4 * ci)) / model.scale_factor  # once per video, shared by the four prompts (:98)
+            drawn = {batch["video_name"]: load_mask_image(args, *((None, None) if on_region else (image_size, image_size)))}
+        # once per video, shared by the four prompts (:98); a region edit encodes its own working clip
+        cond = None if on_region else model.encode_image_to_latent(frames, **_seeded(seed, 4 * ci)) / model.scale_factor
         todo = []
         for key in kinds:
             prompt = prompts[batch["video_name"]]["edit_" + key] if args.prompt_source == "edit" else batch[key]
@@ -1062,19 +1116,23 @@ def run_dataset(args, model, pipe, rank=0, world=1, scorer=None):
                 print(f"File {gif_path} exists, skip")
                 continue
             todo.append((gif_path, image_dir, dict(frames=frames, text_cond=model.encode_text([prompt]), text_uncond=text_uncond,
-                                                   text_cfg=text_cfg, video_cfg=video_cfg, cond=cond, unit=4 * ci + kinds.index(key),
+                                                   text_cfg=text_cfg, video_cfg=video_cfg, unit=4 * ci + kinds.index(key),
+                                                   **({"cond": cond} if cond is not None else {}), **region_unit(args, image_size),
                                                    strength=getattr(args, "strength", 1.0), **per["all"], **per["masked"](batch["video_name"] in drawn),
                                                    **(dict(mask=drawn[batch["video_name"]], mask_mode=getattr(args, "mask_mode", "max"))
                                                       if batch["video_name"] in drawn else {})), prompt))
         # the four prompts of a video share the conditioning latent and the window plan: one stacked launch chain per window (B = 12)
+        run = edit_videos
+        if on_region:
+            from .region import edit_regions as run
         if getattr(args, "no_stack", False):
-            edits = [edit_videos(model, pipe, [u], seed=seed, **want_masks, **more)[0] for _, _, u, _ in todo]
+            edits = [run(model, pipe, [u], seed=seed, **want_masks, **more)[0] for _, _, u, _ in todo]
         else:
-            edits = edit_videos(model, pipe, [u for _, _, u, _ in todo], seed=seed, max_clips=getattr(args, "max_stack", None), **want_masks, **more)
+            edits = run(model, pipe, [u for _, _, u, _ in todo], seed=seed, max_clips=getattr(args, "max_stack", None), **want_masks, **more)
         for (gif_path, image_dir, u, prompt), edited in zip(todo, edits):
             if want_masks:
                 edited, masks[u["unit"]] = edited
-            records.append(unit_record(args, u["unit"], frames, edited, scorer, lambda: (batch["original"], prompt), masks.get(u["unit"]),
+            records.append(unit_record(args, u["unit"], frames, edited, scorer, lambda: (batch["original"], prompt), region_est(args, masks.get(u["unit"])),
                                        u.get("mask"), estimator))
             save_tensor_to_gif(torch.cat([frames.float().cpu(), edited.float().cpu()], dim=4), gif_path, fps=5)
             save_tensor_to_images(edited.float().cpu(), image_dir)
@@ -1125,11 +1183,12 @@ def main(argv=None):
     if args.synthetic:
         g = torch.Generator().manual_seed(0)
         T, S = args.num_frames[0], args.image_size[0]
-        data = {"frames": torch.rand((args.synthetic, T, 3, S, S), generator=g) * 2 - 1,
+        SW, SH = args.region_source or (S, S)   # (--region-source: the source's own size; --image-size is then the working size)
+        data = {"frames": torch.rand((args.synthetic, T, 3, SH, SW), generator=g) * 2 - 1,
                 "text_cond": torch.randn((args.synthetic, 77, ucfg["cross_attention_dim"]), generator=g),
                 "text_uncond": torch.randn((1, 77, ucfg["cross_attention_dim"]), generator=g)}
         if args.synthetic_mask:
-            data["mask"] = synthetic_mask(args.synthetic, S, S)
+            data["mask"] = synthetic_mask(args.synthetic, SH, SW)
         if args.score_synthetic:   # no captions in a synthetic run: hashed token ids stand in for the source and the edit prompt
             vocab = (synth.CLIP_TINY if args.synthetic_tiny else synth.CLIP_FULL)["vocab_size"]
             data["source_ids"] = synth.synth_token_ids("score.source", args.synthetic, 77, vocab)
@@ -1161,6 +1220,7 @@ def main(argv=None):
     def edit(i):
         m = masks[i:i + 1] if masks is not None else drawn.get(i, image_mask)
         return dict(dict(mask=m, strength=args.strength, mask_mode=args.mask_mode), **per["all"], **per["masked"](m is not None))
+    region = region_unit(args)   # with it the drivers are region.edit_region / edit_regions around the same calls
     scorer = build_scorer(args, f"cuda:{local}", tok)
     records = []
     outs = []
@@ -1168,27 +1228,36 @@ def main(argv=None):
         mine = shard_units(n, rank, world)
         # --seed: units are numbered GLOBALLY (cfg combination ci, unit i of n -> ci * n + i) before they are dealt to the ranks, so a
         # unit keeps its noise streams on every rank, at every world size, stacked or not
-        if args.no_stack:
+        if args.no_stack and region:
+            from .region import edit_region
+            local_out = [edit_region(model, pipe, data["frames"][i:i + 1], data["text_cond"][i:i + 1], data["text_uncond"], text_cfg=text_cfg,
+                                     video_cfg=video_cfg, flows_per_window=flows[i] if flows is not None else None,
+                                     seed=args.seed, unit=ci * n + i, **region, **edit(i), **want_masks, **more) for i in mine]
+        elif args.no_stack:
             local_out = [edit_video(model, pipe, data["frames"][i:i + 1], data["text_cond"][i:i + 1], data["text_uncond"],
                                     text_cfg, video_cfg, flows_per_window=flows[i] if flows is not None else None,
                                     seed=args.seed, unit=ci * n + i, **edit(i), **want_masks, **more) for i in mine]
         else:   # a rank's units as stacked launch chains (run_stacked caps the stack at what the kernels' operand window allows)
             from .inference import max_clips_in_flight
             T, S = data["frames"].shape[1], data["frames"].shape[-1]
-            cap = args.max_stack or max_clips_in_flight(min(T, 16), data["frames"].shape[-2] // 8, S // 8)
+            wh, ww = (region["region"]["size"][1], region["region"]["size"][0]) if region else (data["frames"].shape[-2], S)   # what runs through the UNet
+            cap = args.max_stack or max_clips_in_flight(min(T, 16), wh // 8, ww // 8)
+            run = edit_videos
+            if region:
+                from .region import edit_regions as run
             local_out = []
             for g in range(0, len(mine), cap):
-                local_out += edit_videos(model, pipe, [dict(frames=data["frames"][i:i + 1], text_cond=data["text_cond"][i:i + 1],
-                                                            text_uncond=data["text_uncond"], text_cfg=text_cfg, video_cfg=video_cfg, unit=ci * n + i, **edit(i),
-                                                            **({"flows_per_window": flows[i]} if flows is not None else {}))
-                                                       for i in mine[g:g + cap]], seed=args.seed, max_clips=args.max_stack, **want_masks, **more)
+                local_out += run(model, pipe, [dict(frames=data["frames"][i:i + 1], text_cond=data["text_cond"][i:i + 1],
+                                                    text_uncond=data["text_uncond"], text_cfg=text_cfg, video_cfg=video_cfg, unit=ci * n + i, **edit(i), **region,
+                                                    **({"flows_per_window": flows[i]} if flows is not None else {}))
+                                               for i in mine[g:g + cap]], seed=args.seed, max_clips=args.max_stack, **want_masks, **more)
         if want_masks:
             for i, (_, est) in zip(mine, local_out):
                 est_masks[ci * n + i] = est
             local_out = [img for img, _ in local_out]
         for i, edited in zip(mine, local_out if scorer is not None or want_pixel_scores(args) else []):
             records.append(unit_record(args, ci * n + i, data["frames"][i:i + 1], edited, scorer, lambda: _score_texts(data, i, scorer),
-                                       est_masks.get(ci * n + i), edit(i)["mask"], estimator))
+                                       region_est(args, est_masks.get(ci * n + i)), edit(i)["mask"], estimator))
         local_out = torch.cat(local_out, 0).half() if local_out else torch.zeros((0, *item_shape), device=model.unet.device).half()
         outs.append(gather_frames(local_out, n, item_shape=item_shape))
     if scorer is not None or want_pixel_scores(args):

@@ -29,7 +29,8 @@ def _to_tensor(rgb_uint8):
 
 class LoveuTgveVideoDataset:
     def __init__(self, root_dir, image_size=(480, 480)):
-        self.root_dir, self.image_size = root_dir, tuple(image_size)
+        # image_size=None keeps every frame at its native size (``region.edit_region`` edits a box of it at the working size)
+        self.root_dir, self.image_size = root_dir, (None if image_size is None else tuple(image_size))
         self.data = {}
         source_folder = None
         with open(os.path.join(root_dir, "LOVEU-TGVE-2023_Dataset.csv"), "r") as f:
@@ -62,13 +63,15 @@ class LoveuTgveVideoDataset:
                 ret, frame = cap.read()
                 if not ret:
                     break
-                frame = cv2.cvtColor(cv2.resize(frame, self.image_size), cv2.COLOR_BGR2RGB)
+                frame = cv2.cvtColor(frame if self.image_size is None else cv2.resize(frame, self.image_size), cv2.COLOR_BGR2RGB)
                 frames.append(_to_tensor(frame))
             cap.release()
         elif os.path.isdir(frame_dir):
             from PIL import Image
             for name in sorted(n for n in os.listdir(frame_dir) if n.lower().endswith(_IMG_EXT)):
-                img = Image.open(os.path.join(frame_dir, name)).convert("RGB").resize(self.image_size, Image.BILINEAR)
+                img = Image.open(os.path.join(frame_dir, name)).convert("RGB")
+                if self.image_size is not None:
+                    img = img.resize(self.image_size, Image.BILINEAR)
                 frames.append(_to_tensor(np.asarray(img)))
         else:
             raise FileNotFoundError(f"{mp4} needs OpenCV (not installed) and no frame directory {frame_dir} exists")
@@ -104,7 +107,8 @@ class LoveuTgveVideoDataset:
 def load_mask(path, image_size):
     """A mask from image files: ``path`` is one image -> [1,1,H,W] (a still mask for every frame), or a directory of images, sorted by
     name -> [1,T,H,W] (one per frame).  Read as PIL mode "L" (8-bit grey; white = edit), resized to ``image_size`` = (W, H) with the
-    bilinear resize the frames get (``LoveuTgveVideoDataset.load_frames``) and divided by 255: float32 in [0, 1]."""
+    bilinear resize the frames get (``LoveuTgveVideoDataset.load_frames``) and divided by 255: float32 in [0, 1].  ``image_size=None`` keeps
+    the images' native size (they must then share one)."""
     from PIL import Image
     if os.path.isdir(path):
         names = [os.path.join(path, n) for n in sorted(os.listdir(path)) if n.lower().endswith(_IMG_EXT)]
@@ -114,8 +118,11 @@ def load_mask(path, image_size):
         names = [path]
     else:
         raise FileNotFoundError(f"mask image {path} is neither a file nor a directory")
-    size = tuple(int(s) for s in image_size)
-    planes = [torch.from_numpy(np.array(Image.open(n).convert("L").resize(size, Image.BILINEAR), dtype=np.uint8)).float() / 255.0 for n in names]
+    size = None if image_size is None else tuple(int(s) for s in image_size)
+    images = [Image.open(n).convert("L") for n in names]
+    planes = [torch.from_numpy(np.array(im if size is None else im.resize(size, Image.BILINEAR), dtype=np.uint8)).float() / 255.0 for im in images]
+    if len({tuple(p.shape) for p in planes}) > 1:
+        raise ValueError(f"the mask images in {path} differ in size: pass a size to resize them to")
     return torch.stack(planes, dim=0)[None]
 
 
