@@ -1249,6 +1249,58 @@ typedef struct insv2v_region_paste_desc {
 } insv2v_region_paste_desc;
 int insv2v_region_paste(const insv2v_region_paste_desc* d, insv2v_stream_t stream);
 
+/*
+ * ---- a region that follows the object: one real-valued box per frame (additions to ABI 15: no existing struct or entry changes) -----------
+ * The two entries above with a TRACK in place of the box: n boxes (x0, y0, x1, y1) of doubles, one per frame, read on the HOST
+ * (csrc/region.hip; tests/region_track_ref.py restates the definition in float64).  A box is half-open in continuous
+ * pixel coordinates - pixel j covers [j, j + 1), its centre is j + 0.5 - finite, with x1 > x0 and y1 > y0, inside [0, W] x [0, H].  A
+ * frame's COVER is the integer box [floor(x0), ceil(x1)) x [floor(y0), ceil(y1)).
+ *
+ * RESAMPLE (box -> working size), per axis: n_out destination samples, e = x1 - x0, X0 = floor(x0), n_in = ceil(x1) - X0,
+ * scale = e / n_out, s = max(scale, 1), and for destination index i the centre in cover coordinates c = (x0 - X0) + scale (i + 0.5);
+ * the tap range and the weights are those of the entries above with this c and this n_in.  The taps are clipped at the COVER: the
+ * working clip depends on the cover's pixels only, and for an integer box (cover = box, x0 - X0 = 0.0, e = n_in) the operator is the one
+ * above, bit for bit.  A consequence: as x0 crosses an integer the cover gains or loses a column, and the outputs within support s of
+ * that edge change discontinuously, by a renormalisation; those pixels lie under the paste's ramp.
+ *
+ * PASTE (working size -> each frame's cover), per axis: the source is the working image of n_w samples, scale' = n_w / e,
+ * s = max(scale', 1), c = scale' (X + 0.5 - x0) for the cover's pixel X; taps clipped to [0, n_w) and normalised.
+ * ramp = clamp(d / blend, 0, 1), d = the distance from the pixel's centre to the nearest box edge that is not a frame border (negative
+ * outside the box); an edge is a frame border only when x0 == 0, x1 == W, y0 == 0 or y1 == H exactly; blend == 0: 1 where the centre
+ * lies inside the box, else 0; no such edge: 1.  For an integer box this is min(1, (d_int + 0.5) / blend).  The modes, the operand formed
+ * as it is loaded, add == 0 ? src : src + add, the mask resampled bilinearly and clamped to [0, 1], the final clip and the read before the
+ * write by the same thread are those of insv2v_region_paste; only the cover is written, and a pixel whose ramp is 0 keeps the source
+ * (what was resampled for it is not used).
+ *
+ * The boxes travel to the kernels by value, in launches of at most 64 frames (2 KiB of arguments): no device buffer, no allocation,
+ * no synchronisation.  Every output is a sum in tap order by one thread: two calls give the same bits.  INSV2V_EINVAL before the first
+ * launch, outputs untouched: everything the entries above refuse; boxes == NULL; a coordinate that is not finite; an empty box; a box
+ * outside the frame; a per-axis ratio e / working size outside [1/8, 8] for any frame.
+ */
+typedef struct insv2v_region_resample_track_desc {
+    const float* src;          /* [n,C,H,W] view */
+    int64_t src_stride_n, src_stride_c, src_stride_h;
+    float* dst;                /* [n,C,h,w] contiguous */
+    const double* boxes;       /* HOST pointer, [n][4]: (x0, y0, x1, y1) per frame */
+    int32_t n, C, H, W, h, w;
+    int32_t filter, clamp;
+    float clamp_lo, clamp_hi;
+} insv2v_region_resample_track_desc;
+int insv2v_region_resample_track(const insv2v_region_resample_track_desc* d, insv2v_stream_t stream);
+typedef struct insv2v_region_paste_track_desc {
+    const float* edit;         /* [n,C,h,w] contiguous */
+    const float* down;         /* [n,C,h,w] contiguous (residual mode) */
+    const float* mask;         /* [n,h,w] or NULL (replace mode) */
+    int64_t mask_stride_n;
+    float* out;                /* [n,C,H,W] view: holds the source, only each frame's cover is written */
+    int64_t out_stride_n, out_stride_c, out_stride_h;
+    const double* boxes;       /* HOST pointer, [n][4] */
+    int32_t n, C, H, W, h, w;
+    int32_t mode;
+    float blend;
+} insv2v_region_paste_track_desc;
+int insv2v_region_paste_track(const insv2v_region_paste_track_desc* d, insv2v_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

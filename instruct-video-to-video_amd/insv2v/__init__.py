@@ -17,6 +17,7 @@ def __getattr__(name):
         "warp_image": ".flow_utils", "resize_flow": ".flow_utils", "split_batch": ".run_loveu_tgve",
         "edit_video": ".run_loveu_tgve", "keyframe_fill": ".keyfill", "key_frames": ".keyfill",
         "edit_region": ".region", "edit_regions": ".region", "region_plan": ".region",
+        "track_plan": ".region_track",
     }
     if name in table:
         return getattr(importlib.import_module(table[name], __name__), name)

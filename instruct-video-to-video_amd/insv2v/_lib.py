@@ -227,6 +227,20 @@ class RegionPasteDesc(C.Structure):
                 ("x0", c_i32), ("y0", c_i32), ("x1", c_i32), ("y1", c_i32), ("mode", c_i32), ("blend", c_f32)]
 
 
+class RegionResampleTrackDesc(C.Structure):
+    """insv2v_region_resample_track_desc (csrc/region.hip): ``boxes`` is a HOST pointer to n x 4 doubles."""
+    _fields_ = [("src", c_p), ("src_stride_n", c_i64), ("src_stride_c", c_i64), ("src_stride_h", c_i64), ("dst", c_p), ("boxes", c_p),
+                ("n", c_i32), ("C", c_i32), ("H", c_i32), ("W", c_i32), ("h", c_i32), ("w", c_i32),
+                ("filter", c_i32), ("clamp", c_i32), ("clamp_lo", c_f32), ("clamp_hi", c_f32)]
+
+
+class RegionPasteTrackDesc(C.Structure):
+    """insv2v_region_paste_track_desc (csrc/region.hip): ``boxes`` is a HOST pointer to n x 4 doubles."""
+    _fields_ = [("edit", c_p), ("down", c_p), ("mask", c_p), ("mask_stride_n", c_i64), ("out", c_p),
+                ("out_stride_n", c_i64), ("out_stride_c", c_i64), ("out_stride_h", c_i64), ("boxes", c_p),
+                ("n", c_i32), ("C", c_i32), ("H", c_i32), ("W", c_i32), ("h", c_i32), ("w", c_i32), ("mode", c_i32), ("blend", c_f32)]
+
+
 # name -> (restype, argtypes); mirrors include/insv2v_hip.h one to one.
 SIGNATURES = {
     "insv2v_abi_version": (c_i32, []),
@@ -307,6 +321,8 @@ SIGNATURES = {
     "insv2v_mask_bbox": (c_i32, [c_p, c_i64, c_i64, c_i32, c_i32, c_i32, c_f32, c_p, c_p]),
     "insv2v_region_resample": (c_i32, [C.POINTER(RegionResampleDesc), c_p]),
     "insv2v_region_paste": (c_i32, [C.POINTER(RegionPasteDesc), c_p]),
+    "insv2v_region_resample_track": (c_i32, [C.POINTER(RegionResampleTrackDesc), c_p]),
+    "insv2v_region_paste_track": (c_i32, [C.POINTER(RegionPasteTrackDesc), c_p]),
 }
 
 _lib = None

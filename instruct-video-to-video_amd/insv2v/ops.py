@@ -1523,3 +1523,69 @@ def region_paste(out, edit_w, down_src, box, *, mode="residual", blend=8, mask_w
     d.mode, d.blend = _lib.REGION_MODES.index(mode), float(blend)
     check(lib.insv2v_region_paste(_byref(d), _stream()), "insv2v_region_paste")
     return out
+
+
+def _track_boxes(boxes, n, name):
+    """``boxes``: a sequence of n 4-tuples or an [n,4] float64 CPU tensor -> a ctypes array of n x 4 doubles (the entries read it on the
+    host, before they return)."""
+    if torch.is_tensor(boxes):
+        if boxes.is_cuda or boxes.dtype != torch.float64 or boxes.dim() != 2 or boxes.shape[1] != 4:
+            raise _lib.HipKernelError(f"{name}: boxes {tuple(boxes.shape)} ({boxes.dtype}, {boxes.device}) must be an [n,4] float64 CPU tensor")
+        boxes = boxes.tolist()
+    rows = [tuple(float(v) for v in b) for b in boxes]
+    if len(rows) != n or any(len(b) != 4 for b in rows):
+        raise _lib.HipKernelError(f"{name}: {len(rows)} boxes for {n} frames: one (x0, y0, x1, y1) per frame")
+    return (C.c_double * (4 * n))(*[v for b in rows for v in b])
+
+
+def region_resample_track(src, boxes, size, *, mode="bicubic", clamp=None, out=None):
+    """insv2v_region_resample_track: ``region_resample`` with one real-valued box per frame - ``boxes``, n
+    4-tuples (x0, y0, x1, y1) or an [n,4] float64 CPU tensor.  Frame i of ``src`` [n,C,H,W] is resampled from its own box; the taps are
+    clipped at the box's cover [floor(x0), ceil(x1)) x [floor(y0), ceil(y1))."""
+    lib = _lib.load()
+    n, Cn, H, W = _region_view(src, "region_resample_track.src")
+    if mode not in _lib.REGION_FILTERS:
+        raise ValueError(f"region_resample_track: mode {mode!r} is neither 'bicubic' nor 'bilinear'")
+    w, h = (int(v) for v in size)
+    arr = _track_boxes(boxes, n, "region_resample_track")
+    if out is None:
+        out = torch.empty((n, Cn, max(h, 0), max(w, 0)), device=src.device, dtype=torch.float32)
+    _plain(out, (n, Cn, h, w), "region_resample_track.out")
+    d = _lib.RegionResampleTrackDesc()
+    d.src, d.dst, d.boxes = src.data_ptr() or None, out.data_ptr() or None, C.cast(arr, C.c_void_p)
+    d.src_stride_n, d.src_stride_c, d.src_stride_h = src.stride(0), src.stride(1), src.stride(2)
+    d.n, d.C, d.H, d.W, d.h, d.w = n, Cn, H, W, h, w
+    d.filter, d.clamp = _lib.REGION_FILTERS.index(mode), int(clamp is not None)
+    d.clamp_lo, d.clamp_hi = clamp if clamp is not None else (0.0, 0.0)
+    check(lib.insv2v_region_resample_track(_byref(d), _stream()), "insv2v_region_resample_track")
+    return out
+
+
+def region_paste_track(out, edit_w, down_src, boxes, *, mode="residual", blend=8, mask_w=None):
+    """insv2v_region_paste_track, IN PLACE: ``region_paste`` with one real-valued box per frame (``boxes`` as for
+    ``region_resample_track``).  Frame i of ``out`` [n,C,H,W], which holds the source, takes the edit in its own box; only the box's
+    cover is written, under a ramp measured from the box's real edges.  Returns ``out``."""
+    lib = _lib.load()
+    n, Cn, H, W = _region_view(out, "region_paste_track.out")
+    if mode not in _lib.REGION_MODES:
+        raise ValueError(f"region_paste_track: mode {mode!r} is neither 'residual' nor 'replace'")
+    _req(edit_w, torch.float32, "region_paste_track.edit_w")
+    if edit_w.dim() != 4 or tuple(edit_w.shape[:2]) != (n, Cn) or not edit_w.is_contiguous():
+        raise _lib.HipKernelError(f"region_paste_track: edit_w {tuple(edit_w.shape)} must be a contiguous [{n},{Cn},h,w]")
+    h, w = edit_w.shape[2:]
+    arr = _track_boxes(boxes, n, "region_paste_track")
+    d = _lib.RegionPasteTrackDesc()
+    if mode == "residual":
+        _plain(down_src, (n, Cn, h, w), "region_paste_track.down_src")
+        d.down = down_src.data_ptr() or None
+    elif mask_w is not None:
+        _req(mask_w, torch.float32, "region_paste_track.mask_w")
+        if mask_w.dim() != 3 or mask_w.shape[0] not in (1, n) or tuple(mask_w.shape[1:]) != (h, w) or not mask_w.is_contiguous():
+            raise _lib.HipKernelError(f"region_paste_track: mask_w {tuple(mask_w.shape)} must be a contiguous [{n},{h},{w}] or [1,{h},{w}]")
+        d.mask, d.mask_stride_n = mask_w.data_ptr() or None, (h * w if mask_w.shape[0] == n and n > 1 else 0)
+    d.edit, d.out, d.boxes = edit_w.data_ptr() or None, out.data_ptr() or None, C.cast(arr, C.c_void_p)
+    d.out_stride_n, d.out_stride_c, d.out_stride_h = out.stride(0), out.stride(1), out.stride(2)
+    d.n, d.C, d.H, d.W, d.h, d.w = n, Cn, H, W, h, w
+    d.mode, d.blend = _lib.REGION_MODES.index(mode), float(blend)
+    check(lib.insv2v_region_paste_track(_byref(d), _stream()), "insv2v_region_paste_track")
+    return out

@@ -14,6 +14,9 @@ the edit changed back to the source's resolution and lays it over the untouched 
   edit_region      plan, crop, ``edit_video`` on the working clip, paste
   edit_regions     the same around ``edit_videos``: sources of different size share one stacked run
 
+``track=`` of the two drivers (``region_track.py``) gives every frame its own real-valued box that follows the
+object, in place of the one box per unit; ``track=None`` is everything described here.
+
 The drivers are wrappers, not a new per-unit keyword: the inner edit is by construction an ordinary edit of an ordinary clip, so
 ``mask_shape=``, ``stabilize=``, ``keyframes=``, ``strength=``, seeds and stacking keep working, with their guarantees, at working
 resolution.  Consequences: flow dicts passed through (``mask_flows``, ``stabilize_flows``, ``key_flows``, ``flows_per_window``) and
@@ -83,6 +86,29 @@ def _check_size(size):
         raise ValueError(f"region: the working size {w}x{h} must be positive multiples of 8 (one latent cell per 8x8 pixels)")
 
 
+def _mask_box(H, W, w, h, bbox, pad):
+    """Steps (1) - (4) of ``region_plan`` for a bounding box inside the frame (integers in, integers out); ``track_plan`` sizes its
+    boxes with the same steps."""
+    x0, y0, x1, y1 = bbox
+    g = math.ceil(pad * max(x1 - x0, y1 - y0))
+    x0, y0, x1, y1 = x0 - g, y0 - g, x1 + g, y1 + g
+    bw, bh = x1 - x0, y1 - y0
+    if bw * h < bh * w:      # too narrow for the aspect w : h
+        need = -(-bh * w // h)
+        x0 -= (need - bw) // 2
+        x1 = x0 + need
+    elif bh * w < bw * h:    # too flat
+        need = -(-bw * h // w)
+        y0 -= (need - bh) // 2
+        y1 = y0 + need
+    if x1 - x0 >= W:
+        x0, x1 = 0, W
+    if y1 - y0 >= H:
+        y0, y1 = 0, H
+    dx, dy = max(0, -x0) - max(0, x1 - W), max(0, -y0) - max(0, y1 - H)
+    return x0 + dx, y0 + dy, x1 + dx, y1 + dy
+
+
 def region_plan(frame_hw, size, bbox=None, box=None, pad=0.25):
     """The box of a frame of ``frame_hw`` = (H, W) pixels that is edited at the working ``size`` = (w, h).  A pure function of integers:
     no GPU, no library.
@@ -111,23 +137,7 @@ def region_plan(frame_hw, size, bbox=None, box=None, pad=0.25):
             raise ValueError(f"region: the mask is empty in the {W}x{H} frame (no pixel above the threshold): there is no box to edit")
         if x0 < 0 or y0 < 0 or x1 > W or y1 > H:
             raise ValueError(f"region: the mask's bounding box ({x0}, {y0}, {x1}, {y1}) is not inside the {W}x{H} frame")
-        g = math.ceil(pad * max(x1 - x0, y1 - y0))
-        x0, y0, x1, y1 = x0 - g, y0 - g, x1 + g, y1 + g
-        bw, bh = x1 - x0, y1 - y0
-        if bw * h < bh * w:      # too narrow for the aspect w : h
-            need = -(-bh * w // h)
-            x0 -= (need - bw) // 2
-            x1 = x0 + need
-        elif bh * w < bw * h:    # too flat
-            need = -(-bw * h // w)
-            y0 -= (need - bh) // 2
-            y1 = y0 + need
-        if x1 - x0 >= W:
-            x0, x1 = 0, W
-        if y1 - y0 >= H:
-            y0, y1 = 0, H
-        dx, dy = max(0, -x0) - max(0, x1 - W), max(0, -y0) - max(0, y1 - H)
-        x0, y0, x1, y1 = x0 + dx, y0 + dy, x1 + dx, y1 + dy
+        x0, y0, x1, y1 = _mask_box(H, W, w, h, (x0, y0, x1, y1), pad)
     else:
         x0, y0, x1, y1 = 0, 0, W, H
     bw, bh = x1 - x0, y1 - y0
@@ -195,8 +205,12 @@ def paste_back(frames, edit_w, down_src, plan, mask_w=None, device=None):
     return out[None]
 
 
-def _unit_plan(frames, mask, mask_key, params, fn, dev):
-    """The plan of one unit and the mask that is cropped with the frames (None: the inner edit makes its own, or there is none)."""
+def _unit_plan(frames, mask, mask_key, params, fn, dev, track=None):
+    """The plan of one unit and the mask that is cropped with the frames (None: the inner edit makes its own, or there is none).
+    ``track`` (None: one box for the unit): the per-frame boxes of ``region_track``; the plan then holds ``boxes`` in place of ``box``."""
+    if track is not None:
+        from . import region_track
+        return region_track.unit_track_plan(frames, mask, mask_key, params, region_track.check_track(track), fn, dev)
     _check_frames(frames, fn)
     frame_hw, box = tuple(frames.shape[-2:]), params["box"]
     derived = isinstance(mask, str) or mask_key is not None      # the mask exists only inside the inner edit
@@ -229,29 +243,45 @@ def _unpack(res, return_latent, return_mask):
     return res[0], (res[1] if return_latent else None), (res[-1] if return_mask else None)
 
 
+def _crop(frames, drawn, plan, dev):
+    if "boxes" in plan:
+        from .region_track import crop_to_working_track
+        return crop_to_working_track(frames, drawn, plan, device=dev)
+    return crop_to_working(frames, drawn, plan, device=dev)
+
+
 def _finish(frames, plan, down, mask_w, res, return_latent, inner_mask, return_mask):
     image, latent, est = _unpack(res, return_latent, inner_mask)
     edit_w = image.to(torch.float32)
-    full = paste_back(frames, edit_w, down, plan, mask_w=_inner_mask(est, mask_w) if plan["mode"] == "replace" else None, device=edit_w.device)
-    if return_mask:
+    paste = paste_back
+    if "boxes" in plan:
+        from .region_track import paste_back_track as paste
+    full = paste(frames, edit_w, down, plan, mask_w=_inner_mask(est, mask_w) if plan["mode"] == "replace" else None, device=edit_w.device)
+    if return_mask and "boxes" in plan:
+        est = dict(est or {}, region=dict(boxes=plan["boxes"], travel=plan["travel"], size=plan["size"], working=edit_w, down_src=down))
+    elif return_mask:
         est = dict(est or {}, region=dict(box=plan["box"], size=plan["size"], working=edit_w, down_src=down))
     out = (full,) + ((latent,) if return_latent else ()) + ((est,) if return_mask else ())
     return out if len(out) > 1 else full
 
 
 @torch.no_grad()
-def edit_region(model, inf_pipe, frames, text_cond, text_uncond, region=True, **edit_kwargs):
+def edit_region(model, inf_pipe, frames, text_cond, text_uncond, region=True, track=None, **edit_kwargs):
     """``edit_video`` of a region of full-resolution ``frames`` [1,T,3,H,W] (H, W need not be multiples of 8): the plan's box is resampled
     to the working size, ``edit_video`` runs ONCE on that clip with every other keyword passed through (a tensor ``mask`` resampled with
     it), and the result is pasted over the source.  Returns what ``edit_video`` returns, the image fp32 at the source's size; with
     ``return_mask=True`` the dict gains ``region = dict(box, size, working, down_src)``.  ``region``: True or a dict (``check_region``).
     A [1,T,H,W] or [1,1,H,W] tensor mask costs one ``mask_bbox`` launch and one read-back of 16 bytes; ``mask="auto"`` and ``mask_key=``
-    need ``box=`` (module docstring).  Flow dicts, ``cond``, ``enc_noise`` and ``init_noises`` belong to the working clip."""
+    need ``box=`` (module docstring).  Flow dicts, ``cond``, ``enc_noise`` and ``init_noises`` belong to the working clip.
+
+    ``track``: None (one box for the unit), True or a dict (``region_track.check_track``): every frame gets its own real-valued box of one
+    size that follows the per-frame mask [1,T,H,W] (one ``mask_bbox`` launch, one read-back of 16 (T + 1) bytes), or the boxes of
+    ``track=dict(boxes=[...])``; ``region`` then holds ``boxes`` and ``travel`` in place of ``box``."""
     from .run_loveu_tgve import edit_video
     params = check_region(region)
     dev = model.unet.device
-    plan, drawn = _unit_plan(frames, edit_kwargs.get("mask"), edit_kwargs.get("mask_key"), params, "edit_region", dev)
-    down, mask_w = crop_to_working(frames, drawn, plan, device=dev)
+    plan, drawn = _unit_plan(frames, edit_kwargs.get("mask"), edit_kwargs.get("mask_key"), params, "edit_region", dev, track)
+    down, mask_w = _crop(frames, drawn, plan, dev)
     inner = dict(edit_kwargs)
     if mask_w is not None:
         inner["mask"] = mask_w
@@ -266,7 +296,7 @@ def edit_region(model, inf_pipe, frames, text_cond, text_uncond, region=True, **
 @torch.no_grad()
 def edit_regions(model, inf_pipe, units, return_latent=False, return_mask=False, **kwargs):
     """``edit_region`` of several units around ONE ``edit_videos`` call: each unit (a dict as for ``edit_videos``, optionally with
-    ``region``: True or a dict) is planned and cropped alone, the working clips - which share a shape whatever the sources' sizes, as
+    ``region``: True or a dict, and ``track``: True or a dict - tracked and static units share the run) is planned and cropped alone, the working clips - which share a shape whatever the sources' sizes, as
     long as the units share ``size`` - run as one stacked chain, and each result is pasted over its own source.  ``kwargs``: the other
     keywords of ``edit_videos``.  Returns the list of what ``edit_region`` returns per unit."""
     from .run_loveu_tgve import edit_videos
@@ -276,9 +306,9 @@ def edit_regions(model, inf_pipe, units, return_latent=False, return_mask=False,
     prepared, inner_units = [], []
     for u in units:
         params = check_region(u.get("region", True))
-        plan, drawn = _unit_plan(u["frames"], u.get("mask"), u.get("mask_key"), params, "edit_regions", dev)
-        down, mask_w = crop_to_working(u["frames"], drawn, plan, device=dev)
-        inner = {k: v for k, v in u.items() if k != "region"}
+        plan, drawn = _unit_plan(u["frames"], u.get("mask"), u.get("mask_key"), params, "edit_regions", dev, u.get("track"))
+        down, mask_w = _crop(u["frames"], drawn, plan, dev)
+        inner = {k: v for k, v in u.items() if k not in ("region", "track")}
         inner["frames"] = down
         if mask_w is not None:
             inner["mask"] = mask_w

@@ -727,6 +727,11 @@ def build_parser():
     p.add_argument("--region-blend", type=float, default=None, help="with --region: pixels over which the paste ramps in at the box edges (default 8)")
     p.add_argument("--region-source", nargs=2, type=int, default=None, metavar=("W", "H"),
                    help="with --synthetic and --region: the size of the synthetic source frames (default: --image-size)")
+    p.add_argument("--region-track", action="store_true",
+                   help="with --region: the box follows the object (insv2v/region_track.py) - every frame gets its own box of one size, moved by "
+                        "fractions of a pixel along the smoothed centres of the per-frame mask of --mask-file or a --mask-image folder")
+    p.add_argument("--region-track-smooth", type=float, default=None,
+                   help="with --region-track: the sigma in frames of the Gaussian the box centres are smoothed with (default 2; 0: none)")
     return p
 
 
@@ -833,6 +838,21 @@ def check_args(args):
                 raise SystemExit(f"--region / --region-box / --region-pad / --region-mode / --region-blend (working size --image-size {size}): {e}")
         if getattr(args, "region_source", None) is not None and (not args.synthetic or min(args.region_source) < 1):
             raise SystemExit("--region-source W H sets the size of the --synthetic N source frames: it needs --synthetic and two positive numbers")
+        if getattr(args, "region_track", False):
+            from .region_track import check_track
+            try:
+                check_track(region_unit(args)["track"])
+            except ValueError as e:
+                raise SystemExit(f"--region-track / --region-track-smooth: {e}")
+            if getattr(args, "region_box", None) is not None:
+                raise SystemExit("--region-box fixes one box and --region-track moves it: give one of them")
+            if getattr(args, "auto_mask", False) or getattr(args, "mask_key", None) is not None:
+                raise SystemExit("--region-track follows a drawn per-frame mask (--mask-file, a --mask-image folder): the masks of --auto-mask and "
+                                 "--mask-key exist only inside the working-resolution edit")
+        elif getattr(args, "region_track_smooth", None) is not None:
+            raise SystemExit("--region-track-smooth is a parameter of --region-track")
+    elif getattr(args, "region_track", False) or getattr(args, "region_track_smooth", None) is not None:
+        raise SystemExit("--region-track / --region-track-smooth need --region")
     elif any(getattr(args, k, None) is not None for k in ("region_box", "region_pad", "region_mode", "region_blend", "region_source")):
         raise SystemExit("--region-box / --region-pad / --region-mode / --region-blend / --region-source are parameters of --region")
     return args
@@ -966,7 +986,7 @@ def region_unit(args, image_size=None):
     """What --region adds to every unit (nothing without it): ``region=`` of ``region.edit_region`` with the working size --image-size
     (``image_size``: that of one combination) and only the values given; the others keep ``check_region``'s defaults.  Without
     --region-box the box comes from the unit's drawn mask; --auto-mask and --mask-key make their mask inside the working-resolution
-    edit, so they take the whole frame."""
+    edit, so they take the whole frame.  --region-track adds ``track=`` (True, or the --region-track-smooth given)."""
     if not getattr(args, "region", False):
         return {}
     S = args.image_size[0] if image_size is None else image_size
@@ -978,6 +998,9 @@ def region_unit(args, image_size=None):
     for k in ("pad", "mode", "blend"):
         if getattr(args, "region_" + k, None) is not None:
             r[k] = getattr(args, "region_" + k)
+    if getattr(args, "region_track", False):   # the extra entry only with the switch: ``track=`` of the same drivers
+        smooth = getattr(args, "region_track_smooth", None)
+        return dict(region=r, track=True if smooth is None else dict(smooth=smooth))
     return dict(region=r)
 
 
