@@ -719,6 +719,61 @@ typedef struct insv2v_maskstep_desc {
     float k_src, k_noise;
 } insv2v_maskstep_desc;
 int insv2v_cfg_step_mask(const insv2v_maskstep_desc* d, insv2v_stream_t stream);
+/*
+ * Released form of insv2v_cfg_step_mask (per-pixel edit strength; tests/strength_map_ref.py is the definition):
+ * every latent cell carries the index of the step that releases it to the model, and until then it is held like a cell outside the mask:
+ *   m_eff      = release[f,y,x] <= step ? m : 0             (m = mask[f,y,x], or 1 with mask == NULL)
+ *   latent_out = m_eff*prev + (1 - m_eff)*known             (known as for insv2v_cfg_step_mask)
+ * `step` is the GLOBAL index of the step in the scheduler's timesteps (start_time + i of a partial edit), the index `release` was built
+ * against (insv2v_strength_release).  The gate is the only new arithmetic: the blend expression behind it is the mask form's, and pred_x0
+ * and eps_out stay the model's own.  With release == NULL the call IS insv2v_cfg_step_mask (the same kernels: bit-identical results).
+ * The descriptor holds the fields of insv2v_maskstep_desc in their order, then:
+ *   release      int32 [F,h,w] or NULL
+ *   step         >= 0
+ * INSV2V_EINVAL (before any launch): a release map without src, known_noise or latent_out; step < 0; F, h or w <= 0; release, mask, src,
+ * known_noise or x0_hist overlapping the range of latent_out, pred_x0 or eps_out.
+ * An addition to ABI 15: the existing descriptors, entries and kernels are unchanged.
+ */
+typedef struct insv2v_relstep_desc {
+    const float* eps_in;
+    const float* latent;
+    const float* latent_ref;
+    const float* delta_q;
+    const float* noise;
+    const float* rescale_stats;
+    float* latent_out;
+    float* pred_x0;
+    float* eps_out;
+    int32_t nbranch, F, h, w, R;
+    int32_t correct;
+    float text_cfg, img_cfg;
+    float sqrt_a, sqrt_1ma;
+    float c_x0, c_eps, c_xt, c_noise;
+    float guidance_rescale;
+    int64_t branch_stride;
+    int64_t noise_seed, noise_stream;
+    int32_t noise_on;
+    const float* x0_hist;
+    float c_hist;
+    const float* mask;
+    const float* src;
+    const float* known_noise;
+    float k_src, k_noise;
+    const int32_t* release;
+    int32_t step;
+} insv2v_relstep_desc;
+int insv2v_cfg_step_release(const insv2v_relstep_desc* d, insv2v_stream_t stream);
+/*
+ * Strength image -> release map and pixel gate, one launch, no atomics, no read-back:
+ *   s_c     = the cell value insv2v_mask_to_latent(smap, mode) gives, bit for bit (the same device function)
+ *   n_exec  = 0 if s_c <= 0 or NaN, else min(steps, max(1, floor((double)s_c * steps + 0.5)))   (formed in double: exact for steps <= 2^20)
+ *   release [N,H/8,W/8] int32 = steps - n_exec            (in [0, steps]; steps = the cell is never released)
+ *   gate    [N,H,W] fp32      = 0 where smap <= 0 or NaN, elsewhere mask_img (or 1 with mask_img == NULL); not written when gate == NULL
+ * INSV2V_EINVAL: H or W not a positive multiple of 8; N <= 0; steps outside [1, 2^20]; mode not 0 or 1; NULL smap or release; gate
+ * overlapping smap or mask_img.
+ */
+int insv2v_strength_release(const float* smap, const float* mask_img, int32_t* release, float* gate, int32_t N, int32_t H, int32_t W,
+                            int32_t mode, int32_t steps, insv2v_stream_t stream);
 /* Image-resolution mask fp32 [N,H,W] -> latent resolution [N,H/8,W/8]: per 8x8 cell its mean (mode 0; a pairwise sum, so a mask in
  * [0,1] is within 6 * 2^-24 of the exact mean) or its maximum (mode 1).  H and W must be positive multiples of 8 (any such size);
  * everything else returns INSV2V_EINVAL. */

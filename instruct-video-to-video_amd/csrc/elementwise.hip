@@ -92,9 +92,15 @@ struct cfg_mask_args {
     const float* known_noise;  // [F,4,h,w]
     float k_src, k_noise;
 };
-template <bool MS, bool MASK = false>
+// REL: the released form (insv2v_cfg_step_release) - the masked form with a gate in front of the blend: a cell whose release index lies
+// behind `step` is held (m = 0) whatever its mask says; mk.mask may be NULL (m = 1).  The blend expression itself is the mask form's.
+struct cfg_rel_args {
+    const int32_t* release;    // [F,h,w]
+    int32_t step;
+};
+template <bool MS, bool MASK = false, bool REL = false>
 __device__ __forceinline__ void cfg_step_body(const insv2v_step_desc& p, int do_step, const float* x0_hist, float c_hist,
-                                              const cfg_mask_args& mk = cfg_mask_args{}) {
+                                              const cfg_mask_args& mk = cfg_mask_args{}, const cfg_rel_args& rl = cfg_rel_args{}) {
     const int64_t hw = (int64_t)p.h * p.w;
     int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= 4 * hw) return;
@@ -135,7 +141,13 @@ __device__ __forceinline__ void cfg_step_body(const insv2v_step_desc& p, int do_
             else if (p.noise_on) prev += p.c_noise * rng_normal_at(p.noise_seed, p.noise_stream, li);
             if (p.pred_x0) p.pred_x0[li] = x0;
             if constexpr (MASK) {
-                const float m = mk.mask[(int64_t)f * hw + r];
+                float m;
+                if constexpr (REL) {
+                    m = mk.mask ? mk.mask[(int64_t)f * hw + r] : 1.f;
+                    if (rl.release[(int64_t)f * hw + r] > rl.step) m = 0.f;   // release <= step ? m : 0
+                } else {
+                    m = mk.mask[(int64_t)f * hw + r];
+                }
                 const float known = mk.k_src * mk.src[li] + mk.k_noise * mk.known_noise[li];
                 prev = m * prev + (1.f - m) * known;   // m == 0: exactly `known`, whatever the model predicted
             }
@@ -150,6 +162,10 @@ __global__ void cfg_step_ms_kernel(insv2v_step_desc p, int do_step, const float*
 template <bool MS>
 __global__ void cfg_step_mask_kernel(insv2v_step_desc p, int do_step, const float* x0_hist, float c_hist, cfg_mask_args mk) {
     cfg_step_body<MS, true>(p, do_step, x0_hist, c_hist, mk);
+}
+template <bool MS>
+__global__ void cfg_step_release_kernel(insv2v_step_desc p, const float* x0_hist, float c_hist, cfg_mask_args mk, cfg_rel_args rl) {
+    cfg_step_body<MS, true, true>(p, 1, x0_hist, c_hist, mk, rl);
 }
 // argument checks shared by both entry points; normalises d in place
 static int cfg_step_check(insv2v_step_desc& d) {
@@ -230,15 +246,53 @@ extern "C" int insv2v_cfg_step_mask(const insv2v_maskstep_desc* kp, insv2v_strea
     else hipLaunchKernelGGL(cfg_step_mask_kernel<true>, grid, dim3(128), 0, as_stream(stream), d, 1, hist, kp->c_hist, mk);
     return launch_status();
 }
+extern "C" int insv2v_cfg_step_release(const insv2v_relstep_desc* rp, insv2v_stream_t stream) {
+    if (!rp) return INSV2V_EINVAL;
+    // insv2v_relstep_desc = the fields of insv2v_maskstep_desc, in their order, then release and step
+    static_assert(offsetof(insv2v_relstep_desc, release) == sizeof(insv2v_maskstep_desc) &&
+                  offsetof(insv2v_relstep_desc, mask) == offsetof(insv2v_maskstep_desc, mask) &&
+                  offsetof(insv2v_relstep_desc, k_noise) == offsetof(insv2v_maskstep_desc, k_noise) &&
+                  offsetof(insv2v_relstep_desc, x0_hist) == offsetof(insv2v_maskstep_desc, x0_hist) &&
+                  offsetof(insv2v_relstep_desc, noise_on) == offsetof(insv2v_maskstep_desc, noise_on) &&
+                  offsetof(insv2v_relstep_desc, branch_stride) == offsetof(insv2v_maskstep_desc, branch_stride),
+                  "insv2v_relstep_desc must begin with the fields of insv2v_maskstep_desc");
+    // without a release map this IS insv2v_cfg_step_mask (and, without a mask, what that dispatches to): the same kernels, so the results
+    // are bit-identical - a dispatch and not a runtime `if`, for the reason given there
+    if (!rp->release) {
+        insv2v_maskstep_desc k;
+        memcpy(&k, rp, sizeof(k));
+        return insv2v_cfg_step_mask(&k, stream);
+    }
+    insv2v_step_desc d;
+    memcpy(&d, rp, sizeof(d));
+    if (int rc = cfg_step_check(d)) return rc;
+    if (!rp->src || !rp->known_noise || !d.latent_out || rp->step < 0) return INSV2V_EINVAL;
+    const float* hist = rp->x0_hist;
+    if (!hist && rp->c_hist != 0.f) return INSV2V_EINVAL;
+    if (d.F <= 0 || d.h <= 0 || d.w <= 0) return INSV2V_EINVAL;
+    const uintptr_t bytes = (uintptr_t)(4ll * d.F * d.h * d.w) * sizeof(float);
+    const struct { uintptr_t b, n; } reads[] = {{(uintptr_t)rp->release, bytes / 4}, {(uintptr_t)rp->mask, bytes / 4}, {(uintptr_t)rp->src, bytes},
+                                                {(uintptr_t)rp->known_noise, bytes}, {(uintptr_t)hist, bytes}};
+    for (uintptr_t ob : {(uintptr_t)d.latent_out, (uintptr_t)d.pred_x0, (uintptr_t)d.eps_out})   // these are read while the outputs are written
+        for (const auto& rd : reads)
+            if (rd.b && ob && rd.b < ob + bytes && ob < rd.b + rd.n) return INSV2V_EINVAL;
+    const cfg_mask_args mk{rp->mask, rp->src, rp->known_noise, rp->k_src, rp->k_noise};
+    const cfg_rel_args rl{rp->release, rp->step};
+    const int64_t n = 4ll * d.h * d.w;
+    const dim3 grid((unsigned)((n + 127) / 128));
+    if (!hist) hipLaunchKernelGGL(cfg_step_release_kernel<false>, grid, dim3(128), 0, as_stream(stream), d, (const float*)nullptr, 0.f, mk, rl);
+    else hipLaunchKernelGGL(cfg_step_release_kernel<true>, grid, dim3(128), 0, as_stream(stream), d, hist, rp->c_hist, mk, rl);
+    return launch_status();
+}
 
 // ---- masks (localized edits): image-resolution mask -> latent resolution, the final composite, and the re-noised source latent
 __device__ __forceinline__ float mask_tree8(const float* v, int mode) {   // pairwise: 3 roundings per level of 8, not 7
     if (mode) return fmaxf(fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3])), fmaxf(fmaxf(v[4], v[5]), fmaxf(v[6], v[7])));
     return ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7]));
 }
-__global__ __launch_bounds__(256) void mask_to_latent_kernel(const float* __restrict__ mask, float* __restrict__ out, int64_t total, int h, int w, int mode) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;   // over [N, h, w] cells
-    if (i >= total) return;
+// the value of latent cell i of [N, h, w] (w cells per row): the mean (mode 0) or maximum (mode 1) of its 8x8 pixels - THE cell reduction,
+// shared by insv2v_mask_to_latent and insv2v_strength_release
+__device__ __forceinline__ float mask_cell_value(const float* __restrict__ mask, int64_t i, int w, int mode) {
     const int x = (int)(i % w);
     const int64_t ny = i / w;                                     // n * h + y: the cell's first image row is 8 * ny
     const float* cell = mask + (ny * 8) * ((int64_t)w * 8) + (int64_t)x * 8;
@@ -251,7 +305,12 @@ __global__ __launch_bounds__(256) void mask_to_latent_kernel(const float* __rest
         rows[j] = mask_tree8(v, mode);
     }
     const float s = mask_tree8(rows, mode);
-    out[i] = mode ? s : s * 0.015625f;
+    return mode ? s : s * 0.015625f;
+}
+__global__ __launch_bounds__(256) void mask_to_latent_kernel(const float* __restrict__ mask, float* __restrict__ out, int64_t total, int h, int w, int mode) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;   // over [N, h, w] cells
+    if (i >= total) return;
+    out[i] = mask_cell_value(mask, i, w, mode);
 }
 extern "C" int insv2v_mask_to_latent(const float* mask, float* out, int32_t N, int32_t H, int32_t W, int32_t mode, insv2v_stream_t stream) {
     if (!mask || !out || N <= 0 || H <= 0 || W <= 0 || (H & 7) || (W & 7) || (mode != 0 && mode != 1)) return INSV2V_EINVAL;
@@ -259,6 +318,45 @@ extern "C" int insv2v_mask_to_latent(const float* mask, float* out, int32_t N, i
     const int64_t grid = (total + 255) / 256;
     if (grid > 0x7fffffffll) return INSV2V_EINVAL;
     hipLaunchKernelGGL(mask_to_latent_kernel, dim3((unsigned)grid), dim3(256), 0, as_stream(stream), mask, out, total, H / 8, W / 8, (int)mode);
+    return launch_status();
+}
+// ---- per-pixel edit strength: strength image -> release map [N,h,w] (one thread per cell, as above) and the
+// pixel gate [N,8h,8w] of the cell's 64 pixels.  The quantisation is strength_to_start's, formed in double: for an fp32 cell value and
+// steps <= 2^20 the product and the sum are exact, so there is no tie case and no dependence on contraction.
+__global__ __launch_bounds__(256) void strength_release_kernel(const float* __restrict__ smap, const float* __restrict__ mask_img, int32_t* __restrict__ release,
+                                                               float* __restrict__ gate, int64_t total, int h, int w, int mode, int steps) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;   // over [N, h, w] cells
+    if (i >= total) return;
+    const float s = mask_cell_value(smap, i, w, mode);
+    int n_exec = 0;
+    if (s > 0.f) {   // (false for NaN)
+        const double q = floor((double)s * (double)steps + 0.5);
+        n_exec = q >= (double)steps ? steps : (q < 1.0 ? 1 : (int)q);
+    }
+    release[i] = steps - n_exec;
+    if (!gate) return;
+    const int64_t first = ((i / w) * 8) * ((int64_t)w * 8) + (int64_t)(i % w) * 8;   // the cell's first pixel, as in mask_cell_value
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const int64_t px = first + (int64_t)j * w * 8 + k;
+            const float v = smap[px];
+            gate[px] = v > 0.f ? (mask_img ? mask_img[px] : 1.f) : 0.f;
+        }
+}
+extern "C" int insv2v_strength_release(const float* smap, const float* mask_img, int32_t* release, float* gate, int32_t N, int32_t H, int32_t W,
+                                       int32_t mode, int32_t steps, insv2v_stream_t stream) {
+    if (!smap || !release || N <= 0 || H <= 0 || W <= 0 || (H & 7) || (W & 7) || (mode != 0 && mode != 1) || steps < 1 || steps > (1 << 20))
+        return INSV2V_EINVAL;
+    const int64_t total = (int64_t)N * (H / 8) * (W / 8);
+    const uintptr_t bytes = (uintptr_t)total * 64 * sizeof(float), g = (uintptr_t)gate;
+    for (uintptr_t rd : {(uintptr_t)smap, (uintptr_t)mask_img})   // read by other threads while the gate is written
+        if (g && rd && rd < g + bytes && g < rd + bytes) return INSV2V_EINVAL;
+    const int64_t grid = (total + 255) / 256;
+    if (grid > 0x7fffffffll) return INSV2V_EINVAL;
+    hipLaunchKernelGGL(strength_release_kernel, dim3((unsigned)grid), dim3(256), 0, as_stream(stream), smap, mask_img, release, gate, total, H / 8, W / 8,
+                       (int)mode, (int)steps);
     return launch_status();
 }
 // (no __restrict__: out may be edited)

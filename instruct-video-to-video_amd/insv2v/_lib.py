@@ -131,6 +131,11 @@ class MaskStepDesc(C.Structure):
     _fields_ = MStepDesc._fields_ + [("mask", c_p), ("src", c_p), ("known_noise", c_p), ("k_src", c_f32), ("k_noise", c_f32)]
 
 
+class RelStepDesc(C.Structure):
+    """insv2v_relstep_desc: MaskStepDesc's fields in their order, then the release map (int32 [F,h,w]) and the step's global index."""
+    _fields_ = MaskStepDesc._fields_ + [("release", c_p), ("step", c_i32)]
+
+
 class Im2colDesc(C.Structure):
     _fields_ = [("x", c_p), ("x2", c_p), ("out", c_p), ("ldx", c_i64), ("ldx2", c_i64), ("ldo", c_i64),
                 ("N", c_i32), ("IH", c_i32), ("IW", c_i32), ("C", c_i32), ("C1", c_i32), ("KH", c_i32), ("KW", c_i32),
@@ -279,6 +284,8 @@ SIGNATURES = {
     "insv2v_cfg_step": (c_i32, [C.POINTER(StepDesc), c_p]),
     "insv2v_cfg_step_ms": (c_i32, [C.POINTER(MStepDesc), c_p]),
     "insv2v_cfg_step_mask": (c_i32, [C.POINTER(MaskStepDesc), c_p]),
+    "insv2v_cfg_step_release": (c_i32, [C.POINTER(RelStepDesc), c_p]),
+    "insv2v_strength_release": (c_i32, [c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_p]),
     "insv2v_mask_to_latent": (c_i32, [c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_p]),
     "insv2v_composite": (c_i32, [c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_p]),
     "insv2v_add_noise": (c_i32, [c_p, c_p, c_p, c_i64, c_f32, c_f32, c_p]),

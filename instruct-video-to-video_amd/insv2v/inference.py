@@ -277,24 +277,36 @@ def _rng_of(kw):
     return (kw["seed"], kw.get("unit", 0), kw.get("window", 0))
 
 
-def check_known_region(latent, mask=None, source_latent=None, known_noise=None):
+def check_known_region(latent, mask=None, source_latent=None, known_noise=None, release=None):
     """Host-side check of a call's masked-edit arguments (no launch): ``mask`` [1,F,h,w] at latent resolution, ``source_latent`` and
-    ``known_noise`` [1,F,4,h,w] like ``latent``; a mask needs both of the others, and they mean nothing without one."""
-    if mask is None:
+    ``known_noise`` [1,F,4,h,w] like ``latent``; a mask needs both of the others, and they mean nothing without one.  ``release`` (an
+    int32 [1,F,h,w] release map) is a known region too, with or without a mask: it needs both of the others."""
+    if mask is None and release is None:
         if source_latent is not None or known_noise is not None:
-            raise ValueError("source_latent / known_noise are the known region of a masked edit: pass mask= with them")
+            raise ValueError("source_latent / known_noise are the known region of a masked edit: pass mask= (or release=) with them")
         return
     if source_latent is None or known_noise is None:
-        raise ValueError("a mask needs source_latent= (the scaled source latent) and known_noise= (the window's initial noise)")
+        raise ValueError(("a mask needs" if release is None else "a release map needs") +
+                         " source_latent= (the scaled source latent) and known_noise= (the window's initial noise)")
     b, F, _, h, w = latent.shape
-    if not torch.is_tensor(mask) or tuple(mask.shape) != (b, F, h, w):
+    if release is not None:
+        if not torch.is_tensor(release) or tuple(release.shape) != (b, F, h, w):
+            raise ValueError(f"release {tuple(getattr(release, 'shape', ()))} must be [{b},{F},{h},{w}]: one release step per latent cell of latent {tuple(latent.shape)}")
+        if release.dtype != torch.int32:
+            raise ValueError(f"release must be an int32 tensor (ops.strength_release's), not {release.dtype}")
+    if mask is not None and (not torch.is_tensor(mask) or tuple(mask.shape) != (b, F, h, w)):
         raise ValueError(f"mask {tuple(getattr(mask, 'shape', ()))} must be [{b},{F},{h},{w}]: one latent-resolution plane per frame of latent {tuple(latent.shape)}")
     for name, t in (("source_latent", source_latent), ("known_noise", known_noise)):
         if not torch.is_tensor(t) or tuple(t.shape) != tuple(latent.shape):
             raise ValueError(f"{name} {tuple(getattr(t, 'shape', ()))} must be shaped like the latent {tuple(latent.shape)}")
 
 
-_KNOWN_KEYS = ("mask", "source_latent", "known_noise")
+_KNOWN_KEYS = ("mask", "source_latent", "known_noise", "release")
+
+
+def _known_of(kw):
+    """The ``known=`` tuple of a call's kwargs (``_KNOWN_KEYS``' order), or None for a call without a known region: a mask or a release map."""
+    return tuple(kw.get(k) for k in _KNOWN_KEYS) if kw.get("mask") is not None or kw.get("release") is not None else None
 
 # ---- a mask estimated from the prompt (DESIGN.md section 18) -------------------------------------------------------------------------
 # Starting values, not findings: nobody has tuned them on a real checkpoint.
@@ -346,13 +358,17 @@ class InferenceIP2PVideo(Inference):
     def zeros(self, x):
         return torch.zeros_like(x)
 
-    def _known_tensors(self, latent, mask=None, source_latent=None, known_noise=None):
-        """The known region of ONE clip on the device - dict(mask [F,h,w], src [F,4,h,w], noise [F,4,h,w]) - or None without a mask.
-        The public entry points have checked it (``check_known_region``)."""
-        if mask is None:
+    def _known_tensors(self, latent, mask=None, source_latent=None, known_noise=None, release=None):
+        """The known region of ONE clip on the device - dict(mask [F,h,w], src [F,4,h,w], noise [F,4,h,w]), with a release map also
+        release (int32 [F,h,w]; mask may then be None) - or None without a mask and a release map.  The public entry points have checked
+        it (``check_known_region``)."""
+        if mask is None and release is None:
             return None
         to = lambda t: t[0].to(device=self.unet.device, dtype=torch.float32).contiguous()
-        return dict(mask=to(mask), src=to(source_latent), noise=to(known_noise))
+        known = dict(mask=None if mask is None else to(mask), src=to(source_latent), noise=to(known_noise))
+        if release is not None:
+            known["release"] = release[0].to(device=self.unet.device, dtype=torch.int32).contiguous()
+        return known
 
     # ---- shared loop ------------------------------------------------------------------------------
     def _clip_tensors(self, latent, img_cond):
@@ -395,7 +411,7 @@ class InferenceIP2PVideo(Inference):
         """One sampling loop as a generator that yields after enqueueing each step's (asynchronous) GPU work,
         so several independent clips can be interleaved from one host thread (``run_concurrent``).
         ``rng`` = (seed, unit, window) or None: where a stochastic scheduler's variance noise comes from (``_finish_step``).
-        ``known`` = (mask, source_latent, known_noise) or None: the known region of a masked edit (``_finish_step``)."""
+        ``known`` = (mask, source_latent, known_noise, release) or None: the known region of a masked edit (``_finish_step``)."""
         known = self._known_tensors(latent, *known) if known is not None else None
         lat, cond, runner = self._prep(latent, text_cond, text_uncond, img_cond, slot)
         dev = lat.device
@@ -411,7 +427,7 @@ class InferenceIP2PVideo(Inference):
             ops.build_unet_input(lat, cond, runner.x_in, runner.t, t, 3)
             eps = runner.run()
             lat, pred = self._finish_step(i, t, eps, lat, text_cfg, img_cfg, guidance_rescale, stats, ref, noise_correct_step, flows, rng=rng,
-                                          hist=hist, t_last=t_last, known=known)
+                                          hist=hist, t_last=t_last, known=known, start_time=start_time)
             hist, t_last = pred, t
             all_latent.append(lat[None])
             all_pred.append(pred[None])
@@ -419,7 +435,7 @@ class InferenceIP2PVideo(Inference):
         return {"latent": lat[None], "all_latent": all_latent, "all_pred": all_pred}
 
     def _finish_step(self, i, t, eps, lat, text_cfg, img_cfg, guidance_rescale, stats, ref, noise_correct_step, flows, noise=None, bstride=0,
-                     rng=None, hist=None, t_last=None, known=None):
+                     rng=None, hist=None, t_last=None, known=None, start_time=0):
         """Everything of one sampling step behind the UNet for ONE clip: CFG combine (+ rescale), noise correction, scheduler
         step (inference.py:197-213, 270-277, 367-386).  eps: the clip's three branch predictions [3*F*h*w, 4] fp32, or (bstride > 0,
         the branch-major stack) a view that starts at its first branch with bstride fp32 elements between the branches.
@@ -429,7 +445,9 @@ class InferenceIP2PVideo(Inference):
         executed step, None on the first: what a multistep scheduler (DPM-Solver++ 2M) builds its second-order term from.
         ``known`` (``_known_tensors``): a masked edit - inside the step kernel the new latent becomes
         ``mask * prev + (1 - mask) * (k_src * src + k_noise * noise)`` with the scheduler's ``known_coefficients(t)``; the x0 prediction
-        stays the model's own.  None: the launches of an unmasked call, unchanged."""
+        stays the model's own.  None: the launches of an unmasked call, unchanged.  With a release map in ``known`` the step kernel also
+        gets ``step = start_time + i``, the step's GLOBAL index in ``scheduler.timesteps`` (``i`` counts the executed steps of a partial
+        edit, a release map counts all of them): a cell stays held until ``release <= step``."""
         dev = lat.device
         F, _, h, w = lat.shape
         if stats is not None:
@@ -459,6 +477,8 @@ class InferenceIP2PVideo(Inference):
         if known is not None:
             k_src, k_noise = self.scheduler.known_coefficients(t)
             ms = dict(ms, mask=known["mask"], src=known["src"], known_noise=known["noise"], k_src=k_src, k_noise=k_noise)
+            if known.get("release") is not None:
+                ms.update(release=known["release"], step=start_time + i)
         new_lat, pred = torch.empty_like(lat), torch.empty_like(lat)
         correct = ref is not None and noise_correct_step * self.num_ddim_steps > i
         common = dict(text_cfg=text_cfg, img_cfg=img_cfg, sqrt_a=co["sqrt_a"], sqrt_1ma=co["sqrt_1ma"],
@@ -564,7 +584,7 @@ class InferenceIP2PVideo(Inference):
                 noise = cl["noises"][i] if cl["noises"] is not None else None
                 cl["lat"], pred = self._finish_step(i, t, eps[c * rows1:], cl["lat"], cl["text_cfg"], cl["img_cfg"], cl["gr"],
                                                     cl["stats"], cl["ref"], cl["ncs"], cl["flows"], noise=noise, bstride=n * rows1 * 4,
-                                                    rng=cl["rng"], hist=cl["hist"], t_last=t_last, known=cl["known"])
+                                                    rng=cl["rng"], hist=cl["hist"], t_last=t_last, known=cl["known"], start_time=st0)
                 cl["hist"] = pred
                 cl["all_latent"].append(cl["lat"][None])
                 cl["all_pred"].append(pred[None])
@@ -628,7 +648,7 @@ class InferenceIP2PVideo(Inference):
             args = dict(latent=kw["latent"], text_cond=kw["text_cond"], text_uncond=kw["text_uncond"], img_cond=kw["img_cond"],
                         text_cfg=kw.get("text_cfg", 7.5), img_cfg=kw.get("img_cfg", 1.2), start_time=kw.get("start_time", 0),
                         guidance_rescale=kw.get("guidance_rescale", 0.0), slot=slot, rng=_rng_of(kw),
-                        known=tuple(kw.get(k) for k in _KNOWN_KEYS) if kw.get("mask") is not None else None)
+                        known=_known_of(kw))
             if kw.get("latent_ref") is not None:
                 args.update(latent_ref=kw["latent_ref"], noise_correct_step=kw.get("noise_correct_step", 1.0))
             gens.append((st, self._loop_gen(**args)))
@@ -716,35 +736,39 @@ class InferenceIP2PVideo(Inference):
     # ---- reference call surface ----------------------------------------------------------------------
     @torch.no_grad()
     def __call__(self, latent, text_cond, text_uncond, img_cond, text_cfg=7.5, img_cfg=1.2, start_time=0,
-                 guidance_rescale=0.0, seed=None, unit=0, window=0, mask=None, source_latent=None, known_noise=None):
+                 guidance_rescale=0.0, seed=None, unit=0, window=0, mask=None, source_latent=None, known_noise=None, release=None):
         """``mask`` [1,F,h,w] in [0,1] at latent resolution (1 = edit, 0 = keep) with ``source_latent`` [1,F,4,h,w] (the SCALED source
         latent, ``model.encode_image_to_latent``'s result) and ``known_noise`` [1,F,4,h,w] (the fixed noise it is re-noised with: the
         window's initial noise): after every step the latent outside the mask is the source's, re-noised to that step's level - inside
         the step kernel, no extra launch.  Without a mask the call launches exactly what it launched before.
         ``seed`` (default None: the draws of ``torch.randn``, as before): a stochastic scheduler's variance noise of step i comes from
         the seeded stream ``rng.stream_id(STEP, unit, window, i)`` - a pure function of (seed, unit, window, step, element), whatever
-        else runs.  Injected ``variance_noises`` win over it; a deterministic scheduler ignores it."""
+        else runs.  Injected ``variance_noises`` win over it; a deterministic scheduler ignores it.
+        ``release`` int32 [1,F,h,w] (``ops.strength_release``'s) with ``source_latent`` and ``known_noise``, with or
+        without a mask: cell c is held like a cell outside the mask through the steps before ``timesteps[release_c]`` and belongs to the
+        model (under its mask value) from that step on - a per-cell ``strength``.  The index is global: ``start_time`` decides which steps
+        run, a release index below it changes nothing more.  Without ``release`` the call launches exactly what it launched before."""
         if latent.shape[0] != 1:
             return self._batched_call(latent, text_cond, text_uncond, img_cond, text_cfg=text_cfg, img_cfg=img_cfg, start_time=start_time,
                                       guidance_rescale=guidance_rescale, seed=seed, unit=unit, window=window,
-                                      mask=mask, source_latent=source_latent, known_noise=known_noise)
-        check_known_region(latent, mask, source_latent, known_noise)
+                                      mask=mask, source_latent=source_latent, known_noise=known_noise, release=release)
+        check_known_region(latent, mask, source_latent, known_noise, release)
         return self._loop(latent, text_cond, text_uncond, img_cond, text_cfg, img_cfg, start_time, guidance_rescale,
                           rng=_rng_of(dict(seed=seed, unit=unit, window=window)),
-                          known=(mask, source_latent, known_noise) if mask is not None else None)
+                          known=_known_of(dict(mask=mask, source_latent=source_latent, known_noise=known_noise, release=release)))
 
     @torch.no_grad()
     def second_clip_forward(self, latent, text_cond, text_uncond, img_cond, latent_ref, noise_correct_step=1.0,
                             text_cfg=7.5, img_cfg=1.2, start_time=0, guidance_rescale=0.0, seed=None, unit=0, window=0,
-                            mask=None, source_latent=None, known_noise=None):
+                            mask=None, source_latent=None, known_noise=None, release=None):
         if latent.shape[0] != 1:
             return self._batched_call(latent, text_cond, text_uncond, img_cond, latent_ref=latent_ref, noise_correct_step=noise_correct_step,
                                       text_cfg=text_cfg, img_cfg=img_cfg, start_time=start_time, guidance_rescale=guidance_rescale,
-                                      seed=seed, unit=unit, window=window, mask=mask, source_latent=source_latent, known_noise=known_noise)
-        check_known_region(latent, mask, source_latent, known_noise)
+                                      seed=seed, unit=unit, window=window, mask=mask, source_latent=source_latent, known_noise=known_noise, release=release)
+        check_known_region(latent, mask, source_latent, known_noise, release)
         return self._loop(latent, text_cond, text_uncond, img_cond, text_cfg, img_cfg, start_time, guidance_rescale,
                           latent_ref=latent_ref, noise_correct_step=noise_correct_step, rng=_rng_of(dict(seed=seed, unit=unit, window=window)),
-                          known=(mask, source_latent, known_noise) if mask is not None else None)
+                          known=_known_of(dict(mask=mask, source_latent=source_latent, known_noise=known_noise, release=release)))
 
 
 class InferenceIP2PVideoOpticalFlow(InferenceIP2PVideo):
@@ -785,8 +809,9 @@ class InferenceIP2PVideoOpticalFlow(InferenceIP2PVideo):
     @torch.no_grad()
     def second_clip_forward(self, latent, text_cond, text_uncond, img_cond, latent_ref, ref_images=None,
                             query_images=None, noise_correct_step=1.0, text_cfg=7.5, img_cfg=1.2, start_time=0,
-                            guidance_rescale=0.0, flows=None, seed=None, unit=0, window=0, mask=None, source_latent=None, known_noise=None):
-        check_known_region(latent, mask, source_latent, known_noise)
+                            guidance_rescale=0.0, flows=None, seed=None, unit=0, window=0, mask=None, source_latent=None, known_noise=None,
+                            release=None):
+        check_known_region(latent, mask, source_latent, known_noise, release)
         if flows is None:
             assert ref_images.shape[0] == 1, "only support batch size 1"
             flows = self.obtain_flow_batched(ref_images[0], query_images[0])
@@ -795,4 +820,4 @@ class InferenceIP2PVideoOpticalFlow(InferenceIP2PVideo):
         return self._loop(latent, text_cond, text_uncond, img_cond, text_cfg, img_cfg, start_time, guidance_rescale,
                           latent_ref=latent_ref, noise_correct_step=noise_correct_step, flows=small,
                           rng=_rng_of(dict(seed=seed, unit=unit, window=window)),
-                          known=(mask, source_latent, known_noise) if mask is not None else None)
+                          known=_known_of(dict(mask=mask, source_latent=source_latent, known_noise=known_noise, release=release)))

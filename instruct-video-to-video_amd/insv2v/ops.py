@@ -11,7 +11,7 @@ import torch
 
 from . import _lib
 from .rng import as_int64
-from ._lib import GemmDesc, GroupNormDesc, LayerNormDesc, AttentionDesc, StepDesc, MStepDesc, MaskStepDesc, MaskTrackDesc, FfnDesc, RowLinDesc, TattnDesc, XattnDesc, WinogradInDesc, WinogradOutDesc, check
+from ._lib import GemmDesc, GroupNormDesc, LayerNormDesc, AttentionDesc, StepDesc, MStepDesc, MaskStepDesc, RelStepDesc, MaskTrackDesc, FfnDesc, RowLinDesc, TattnDesc, XattnDesc, WinogradInDesc, WinogradOutDesc, check
 
 ACT_NONE, ACT_SILU, ACT_GEGLU, ACT_QUICK_GELU = 0, 1, 2, 3
 ACT_RELU, ACT_SIGMOID, ACT_TANH = 4, 5, 6   # the optical-flow network's (insv2v/raft.py)
@@ -753,18 +753,24 @@ def build_unet_input(latent, img_cond, out, t_out, timestep, nbranch, branch_row
 def cfg_step(eps_in, latent, *, nbranch, text_cfg=1.0, img_cfg=1.0, sqrt_a=1.0, sqrt_1ma=0.0, coef=(0, 0, 0, 0),
              latent_out=None, pred_x0=None, eps_out=None, latent_ref=None, correct=0, delta_q=None, noise=None,
              rescale_stats=None, guidance_rescale=0.0, branch_stride=0, noise_seed=None, noise_stream=0, x0_hist=None, c_hist=0.0,
-             mask=None, src=None, known_noise=None, k_src=0.0, k_noise=0.0):
+             mask=None, src=None, known_noise=None, k_src=0.0, k_noise=0.0, release=None, step=0):
     """``noise_seed`` / ``noise_stream``: the step's variance noise is generated inside the kernel from the seeded stream (element = flat
     index of [F,4,h,w]) instead of read from ``noise``; passing both is rejected by the kernel.
     ``x0_hist`` / ``c_hist``: the multistep term ``c_hist * x0_hist`` (the previous step's ``pred_x0``, DPM-Solver++ 2M).  Only a call
     that gives a history goes to insv2v_cfg_step_ms (``cfg_step_ms``); every other call goes to insv2v_cfg_step as before.
     ``mask`` [F,h,w] with ``src`` / ``known_noise`` [F,4,h,w] and ``k_src`` / ``k_noise``: behind the update, ``latent_out`` becomes
     ``mask * prev + (1 - mask) * (k_src * src + k_noise * known_noise)`` (insv2v_cfg_step_mask, ``cfg_step_mask``).  Only a call that
-    gives a mask goes there."""
+    gives a mask goes there.
+    ``release`` int32 [F,h,w] with ``step``, the step's GLOBAL index: a cell is held like one outside the mask until
+    ``release <= step`` (insv2v_cfg_step_release, ``cfg_step_release``; ``mask`` may then be None = 1).  Only a call that gives a
+    release map goes there."""
     kw = dict(nbranch=nbranch, text_cfg=text_cfg, img_cfg=img_cfg, sqrt_a=sqrt_a, sqrt_1ma=sqrt_1ma, coef=coef, latent_out=latent_out,
               pred_x0=pred_x0, eps_out=eps_out, latent_ref=latent_ref, correct=correct, delta_q=delta_q, noise=noise,
               rescale_stats=rescale_stats, guidance_rescale=guidance_rescale, branch_stride=branch_stride, noise_seed=noise_seed,
               noise_stream=noise_stream)
+    if release is not None:
+        return cfg_step_release(eps_in, latent, release=release, step=step, mask=mask, src=src, known_noise=known_noise, k_src=k_src,
+                                k_noise=k_noise, x0_hist=x0_hist, c_hist=c_hist, **kw)
     if mask is not None:
         return cfg_step_mask(eps_in, latent, mask=mask, src=src, known_noise=known_noise, k_src=k_src, k_noise=k_noise, x0_hist=x0_hist,
                              c_hist=c_hist, **kw)
@@ -796,7 +802,57 @@ def cfg_step_mask(eps_in, latent, *, mask=None, src=None, known_noise=None, k_sr
     ``mask``.  ``mask`` fp32 [F,h,w] or None (then the result is bit-identical to ``cfg_step_ms`` / ``cfg_step``); ``src`` and
     ``known_noise`` fp32 [F,4,h,w]; none of them may overlap an output."""
     lib = _lib.load()
-    d = _fill_step_desc(MaskStepDesc(), eps_in, latent, **kw)
+    d = _fill_known_desc(MaskStepDesc(), "cfg_step_mask", eps_in, latent, mask, src, known_noise, k_src, k_noise, x0_hist, c_hist, kw)
+    check(lib.insv2v_cfg_step_mask(_byref(d), _stream()), "insv2v_cfg_step_mask")
+
+
+def cfg_step_release(eps_in, latent, *, release=None, step=0, mask=None, src=None, known_noise=None, k_src=0.0, k_noise=0.0, x0_hist=None,
+                     c_hist=0.0, **kw):
+    """insv2v_cfg_step_release: ``cfg_step_mask`` (its keywords) with a per-cell gate in front of the blend - ``release`` int32 [F,h,w]
+    or None (then the result is bit-identical to ``cfg_step_mask``), ``step`` the step's global index in the scheduler's timesteps: a
+    cell with ``release > step`` is held at the re-noised source whatever ``mask`` says; ``mask`` None means 1 everywhere."""
+    lib = _lib.load()
+    d = _fill_known_desc(RelStepDesc(), "cfg_step_release", eps_in, latent, mask, src, known_noise, k_src, k_noise, x0_hist, c_hist, kw)
+    if release is not None:
+        want = (latent.shape[-4],) + tuple(latent.shape[-2:])
+        _req(release, torch.int32, "release")
+        if tuple(release.shape[-3:]) != want or release.numel() != math.prod(want) or not release.is_contiguous():
+            raise _lib.HipKernelError(f"cfg_step_release: release {tuple(release.shape)} must be contiguous and shaped {want} (latent {tuple(latent.shape)})")
+    if isinstance(step, bool) or not isinstance(step, int) or not -2 ** 31 <= step < 2 ** 31:
+        raise _lib.HipKernelError(f"cfg_step_release: step {step!r} must be an int32")
+    d.release, d.step = _ptr(release), step
+    check(lib.insv2v_cfg_step_release(_byref(d), _stream()), "insv2v_cfg_step_release")
+
+
+def strength_release(smap, steps, mode="max", mask=None):
+    """insv2v_strength_release (tests/strength_map_ref.py is the definition): strength image ``smap`` fp32
+    [..., H, W] in [0,1] -> (release int32 [..., H/8, W/8], gate fp32 [..., H, W]).  ``release`` = ``steps`` minus the steps the cell's
+    strength (``mask_to_latent(smap, mode)``, bit for bit) executes, ``schedulers.strength_to_start`` per cell; ``gate`` = 0 where
+    ``smap`` <= 0 or NaN, elsewhere ``mask`` (an image-resolution mask shaped like ``smap``) or 1."""
+    if mode not in ("mean", "max"):
+        raise ValueError(f"strength_release: mode {mode!r} is neither 'mean' nor 'max'")
+    lib = _lib.load()
+    _req(smap, torch.float32, "strength_release.smap")
+    if smap.dim() < 2:
+        raise _lib.HipKernelError(f"strength_release: smap {tuple(smap.shape)} needs [..., H, W]")
+    smap = smap.contiguous()
+    if mask is not None:
+        _req(mask, torch.float32, "strength_release.mask")
+        if mask.shape != smap.shape:
+            raise _lib.HipKernelError(f"strength_release: mask {tuple(mask.shape)} must be shaped like smap {tuple(smap.shape)}")
+        mask = mask.contiguous()
+    H, W = smap.shape[-2:]
+    N = smap.numel() // max(H * W, 1)
+    release = torch.empty((*smap.shape[:-2], H // 8, W // 8), device=smap.device, dtype=torch.int32)
+    gate = torch.empty_like(smap)
+    check(lib.insv2v_strength_release(smap.data_ptr(), _ptr(mask), release.data_ptr(), gate.data_ptr(), N, H, W, 1 if mode == "max" else 0,
+                                      int(steps), _stream()), "insv2v_strength_release")
+    return release, gate
+
+
+def _fill_known_desc(d, who, eps_in, latent, mask, src, known_noise, k_src, k_noise, x0_hist, c_hist, kw):
+    """The step descriptor ``d`` (MaskStepDesc or one that begins with it) of a call with a known region."""
+    d = _fill_step_desc(d, eps_in, latent, **kw)
     shape = tuple(latent.shape[-4:])
     for name, t, want in (("x0_hist", x0_hist, shape), ("src", src, shape), ("known_noise", known_noise, shape),
                           ("mask", mask, (shape[0],) + shape[2:])):
@@ -804,10 +860,10 @@ def cfg_step_mask(eps_in, latent, *, mask=None, src=None, known_noise=None, k_sr
             continue
         _req(t, torch.float32, name)
         if tuple(t.shape[-len(want):]) != want or t.numel() != math.prod(want) or not t.is_contiguous():
-            raise _lib.HipKernelError(f"cfg_step_mask: {name} {tuple(t.shape)} must be contiguous and shaped {want} (latent {tuple(latent.shape)})")
+            raise _lib.HipKernelError(f"{who}: {name} {tuple(t.shape)} must be contiguous and shaped {want} (latent {tuple(latent.shape)})")
     d.x0_hist, d.c_hist = _ptr(x0_hist), c_hist
     d.mask, d.src, d.known_noise, d.k_src, d.k_noise = _ptr(mask), _ptr(src), _ptr(known_noise), k_src, k_noise
-    check(lib.insv2v_cfg_step_mask(_byref(d), _stream()), "insv2v_cfg_step_mask")
+    return d
 
 
 def mask_to_latent(mask, mode="max"):

@@ -21,7 +21,9 @@ The drivers are wrappers, not a new per-unit keyword: the inner edit is by const
 ``mask_shape=``, ``stabilize=``, ``keyframes=``, ``strength=``, seeds and stacking keep working, with their guarantees, at working
 resolution.  Consequences: flow dicts passed through (``mask_flows``, ``stabilize_flows``, ``key_flows``, ``flows_per_window``) and
 ``cond`` / ``enc_noise`` / ``init_noises`` belong to the WORKING clip; ``mask="auto"`` and ``mask_key=`` produce their mask inside the
-inner edit, so the box cannot be derived from them: pass ``box=(x0, y0, x1, y1)`` or ``box="frame"``.
+inner edit, so the box cannot be derived from them: pass ``box=(x0, y0, x1, y1)`` or ``box="frame"``.  ``strength_map="mask"`` (DESIGN.md
+section 28) passes through - the map is then the resampled mask; a tensor ``strength_map`` raises ValueError, static or tracked: it
+would have to be resampled to the working clip like the mask, which is not built.
 
 ``mode="residual"`` (the default) carries up what the edit CHANGED, ``edit_w - down_src``, and the source keeps its own detail - the
 reasoning of ``keyframes=``'s default; a residual that is exactly zero (outside a hard working-resolution mask, wherever the edit changed
@@ -229,6 +231,14 @@ def _unit_plan(frames, mask, mask_key, params, fn, dev, track=None):
     return dict(plan, mode=params["mode"], blend=params["blend"]), (mask if torch.is_tensor(mask) else None)
 
 
+def _check_strength_map(strength_map, fn):
+    """``strength_map="mask"`` passes through to the inner edit (the mask is resampled with the frames); a tensor map would have to be
+    resampled to the working clip like the mask, which is not built."""
+    if strength_map is not None and not isinstance(strength_map, str):
+        raise ValueError(f"{fn}: a tensor strength_map is not resampled to the working clip (not built): pass strength_map=\"mask\" with a "
+                         "mask, or edit the working clip with edit_video")
+
+
 def _inner_mask(est, mask_w):
     """The replace mode's mask: the composite mask the inner edit used (``shaped``), else its ``mask``, else the resampled drawn one."""
     if isinstance(est, dict):
@@ -279,6 +289,7 @@ def edit_region(model, inf_pipe, frames, text_cond, text_uncond, region=True, tr
     ``track=dict(boxes=[...])``; ``region`` then holds ``boxes`` and ``travel`` in place of ``box``."""
     from .run_loveu_tgve import edit_video
     params = check_region(region)
+    _check_strength_map(edit_kwargs.get("strength_map"), "edit_region")
     dev = model.unet.device
     plan, drawn = _unit_plan(frames, edit_kwargs.get("mask"), edit_kwargs.get("mask_key"), params, "edit_region", dev, track)
     down, mask_w = _crop(frames, drawn, plan, dev)
@@ -304,6 +315,8 @@ def edit_regions(model, inf_pipe, units, return_latent=False, return_mask=False,
         return []
     dev = model.unet.device
     prepared, inner_units = [], []
+    for u in units:
+        _check_strength_map(u.get("strength_map"), "edit_regions")
     for u in units:
         params = check_region(u.get("region", True))
         plan, drawn = _unit_plan(u["frames"], u.get("mask"), u.get("mask_key"), params, "edit_regions", dev, u.get("track"))

@@ -13,7 +13,8 @@ smooth motion steps by whole pixels and the whole working clip would shake by 1 
   paste_back_track       the working-resolution edit laid over each frame's own box: ``ops.region_paste_track``
 
 ``insv2v.region.edit_region(..., track=True)`` and the ``track`` key of ``edit_regions``' units are the drivers.  ``smooth=2.0`` is a
-starting value, NOT tuned here (as every default of sections 18 - 26)."""
+starting value, NOT tuned here (as every default of sections 18 - 26).  As for a static box, ``strength_map="mask"`` passes through to the
+inner edit and a tensor ``strength_map`` raises ValueError there (``region._check_strength_map``): it is not resampled along the track."""
 import math
 
 import torch

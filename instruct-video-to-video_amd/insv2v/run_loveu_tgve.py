@@ -19,6 +19,8 @@ Masks: drawn per frame or still (``mask=``, the "mask" entry of a ``--units`` fi
 ``insv2v/mask_track.py``); ``--mask-image`` reads a drawn mask from a PNG or a folder of PNGs (``video_io.load_mask``).  ``mask_shape=`` /
 ``--mask-grow`` / ``--mask-feather`` grows, shrinks and feathers the mask of any of these sources, once per unit (``insv2v/mask_shape.py``,
 DESIGN.md section 22): the composite gets the soft mask, the latent hold the hard region under it.
+``strength_map=`` / ``--strength-map`` / ``--strength-from-mask`` give every pixel its own edit strength: a latent
+cell is held at the source until the step its strength corresponds to and released to the model from there, inside the step kernel.
 
 ``stabilize=`` / ``--stabilize`` filters a unit's decoded frames along the SOURCE video's optical flow, once per unit and after its last
 window (``insv2v/temporal_filter.py``): the switch to pull when ``--score-warp`` shows flicker.
@@ -78,14 +80,14 @@ KEYFRAME_KEYS = ("stride", "mode", "sigma", "occlusion", "alpha", "beta")
 # ``_EditUnit`` is built from.  A new per-unit feature adds its keywords here (and to ``edit_video``'s signature).  The second row is
 # what ``check_edit_args`` checks, in its parameters' order.
 UNIT_KEYS = ("text_cfg", "video_cfg", "init_noises", "enc_noise", "cond", "flows_per_window",
-             "mask", "strength", "mask_mode", "auto_mask", "mask_key", "mask_flows", "mask_track", "stabilize", "stabilize_flows", "mask_shape",
+             "mask", "strength", "mask_mode", "auto_mask", "mask_key", "mask_flows", "mask_track", "stabilize", "stabilize_flows", "strength_map", "mask_shape",
              "keyframes", "key_flows")
 CHECKED_KEYS = UNIT_KEYS[6:]
 UNIT_DEFAULTS = dict({k: None for k in UNIT_KEYS}, text_cfg=7.5, video_cfg=1.8, strength=1.0, mask_mode="max")
 
 
 def check_edit_args(frames_shape, mask=None, strength=1.0, mask_mode="max", auto_mask=None, mask_key=None, mask_flows=None, mask_track=None,
-                    stabilize=None, stabilize_flows=None, mask_shape=None, keyframes=None, key_flows=None):
+                    stabilize=None, stabilize_flows=None, strength_map=None, mask_shape=None, keyframes=None, key_flows=None):
     """Host-side check of the localized / partial edit controls (nothing is launched): ``strength`` in (0, 1], ``mask_mode`` "mean" or
     "max", ``mask`` a floating-point [1,T,H,W] or [1,1,H,W] tensor for frames [1,T,3,H,W] with H and W multiples of 8 - or the string
     "auto" (the mask is estimated from the prompt, ``InferenceIP2PVideo.estimate_mask``), then optionally with ``auto_mask``, a dict of
@@ -96,13 +98,15 @@ def check_edit_args(frames_shape, mask=None, strength=1.0, mask_mode="max", auto
     video's [T-1,2,H,W] flows.  ``mask_shape`` (None or a dict of ``mask_shape.check_shape_args``' parameters, ``MASK_SHAPE_KEYS``) shapes
     the mask of any source, so it needs one.  ``keyframes`` (None, an int stride or a dict with keys among ``KEYFRAME_KEYS``) optionally
     with ``key_flows``, a dict(fwd=, bwd=) of the source video's [T-1,2,H,W] flows; not together with ``mask="auto"`` (an estimated mask
-    exists on the key frames only)."""
+    exists on the key frames only).  ``strength_map`` (None, a floating-point [1,T,H,W] or [1,1,H,W] tensor in [0,1] for frames with H and
+    W multiples of 8, or the string "mask": the unit's final image mask is the map, so it needs a mask, and not ``mask="auto"``, whose
+    mask is hard)."""
     _check_unit(frames_shape, locals())
 
 
 def _check_unit(frames_shape, u):
     """``check_edit_args`` of a unit's arguments by name (the missing ones at their defaults).  The refusals in their order: key
-    frames, ``mask_shape``, ``stabilize``, the tracked mask, ``mask_mode``, ``auto_mask``, the mask itself."""
+    frames, ``mask_shape``, ``stabilize``, the tracked mask, ``mask_mode``, ``strength_map``, ``auto_mask``, the mask itself."""
     a = {k: u.get(k, UNIT_DEFAULTS[k]) for k in CHECKED_KEYS}
     mask, auto_mask = a["mask"], a["auto_mask"]
     strength_to_start(a["strength"], 1)
@@ -119,6 +123,7 @@ def _check_unit(frames_shape, u):
         _check_track_args(frames_shape, mask, a["mask_key"], a["mask_flows"], a["mask_track"])
     if a["mask_mode"] not in MASK_MODES:
         raise ValueError(f"mask_mode {a['mask_mode']!r} is neither 'mean' nor 'max'")
+    _check_strength_map(frames_shape, mask, a["strength_map"])
     if auto_mask is not None and not (isinstance(mask, str) and mask == "auto"):
         raise ValueError("auto_mask holds the parameters of an estimated mask: pass mask=\"auto\" with it")
     if isinstance(mask, str):
@@ -141,6 +146,27 @@ def _check_unit(frames_shape, u):
         raise ValueError(f"mask {tuple(mask.shape)} must be [1,{T},{H},{W}] or [1,1,{H},{W}] (image resolution) for frames {tuple(frames_shape)}")
     if H % 8 or W % 8:
         raise ValueError(f"a mask needs frame sizes that are multiples of 8 (one latent cell per 8x8 pixels), not {H}x{W}")
+
+
+def _check_strength_map(frames_shape, mask, strength_map):
+    """The ``strength_map`` part of ``check_edit_args``."""
+    if strength_map is None:
+        return
+    if isinstance(strength_map, str):
+        if strength_map != "mask":
+            raise ValueError(f"strength_map must be a tensor, None or the string \"mask\", not {strength_map!r}")
+        if mask is None:
+            raise ValueError("strength_map=\"mask\" makes the unit's image mask its strength map: pass mask= (a tensor, or with mask_key=) with it")
+        if isinstance(mask, str):
+            raise ValueError("strength_map=\"mask\" and mask=\"auto\": an estimated mask is hard (0 or 1), it grades nothing; pass a tensor strength_map")
+        return
+    b, T, _, H, W = frames_shape
+    if not torch.is_tensor(strength_map) or not strength_map.is_floating_point():
+        raise ValueError("strength_map must be a floating-point tensor with values in [0, 1] (1 = fully re-drawn, 0 = never touched) or the string \"mask\"")
+    if strength_map.dim() != 4 or strength_map.shape[0] != 1 or b != 1 or strength_map.shape[1] not in (1, T) or tuple(strength_map.shape[2:]) != (H, W):
+        raise ValueError(f"strength_map {tuple(strength_map.shape)} must be [1,{T},{H},{W}] or [1,1,{H},{W}] (image resolution) for frames {tuple(frames_shape)}")
+    if H % 8 or W % 8:
+        raise ValueError(f"a strength_map needs frame sizes that are multiples of 8 (one latent cell per 8x8 pixels), not {H}x{W}")
 
 
 def _check_params(name, params, keys, check, form=None):
@@ -272,16 +298,19 @@ def _image_mask(mask, T, dev):
 
 
 class _EditPlan:
-    """What a localized (``mask``) or partial (``strength`` < 1) edit adds to the windows of one unit: the source latent z and the
-    latent-resolution mask, split like ``cond``, and the level the trajectory starts from.  ``active`` is False for a plain edit, whose
-    calls then carry no new keyword."""
+    """What a localized (``mask``), partial (``strength`` < 1) or graded (``strength_map``) edit adds to the windows of one unit: the
+    source latent z, the latent-resolution mask and the release map, split like ``cond``, and the level the trajectory starts from.
+    ``active`` is False for a plain edit, whose calls then carry no new keyword.  ``strength_map``: a tensor, or "mask" - the unit's
+    final image mask (``shaped`` with ``mask_shape``) is the map; ``release`` [1,T,h,w] and ``gate`` [T,H,W] are built ONCE
+    (``ops.strength_release``), the composite then uses ``gate`` (``composite_mask``)."""
 
-    def __init__(self, model, inf_pipe, frames, cond, mask, strength, mask_mode, frames_in_batch, num_ref_frames, z=None, mask_shape=None):
+    def __init__(self, model, inf_pipe, frames, cond, mask, strength, mask_mode, frames_in_batch, num_ref_frames, z=None, mask_shape=None,
+                 strength_map=None):
         dev = model.unet.device
         self.start_time = _start_time(inf_pipe, strength)
         partial = strength != 1.0   # (also a strength below 1 that rounds to every step: it starts from the noised source at timesteps[0])
-        self.active = mask is not None or partial
-        self.mask_img = self.masks = self.level = self.shape = None
+        self.active = mask is not None or partial or strength_map is not None
+        self.mask_img = self.masks = self.level = self.shape = self.release = self.releases = self.gate = None
         if not self.active:
             return
         if z is None:   # (a caller's ``cond`` is z / scale_factor)
@@ -299,6 +328,11 @@ class _EditPlan:
                 self.shape = dict(shaped=self.mask_img[None], support=support[None])
                 latent_mask = ops.mask_to_latent(support, "max")
             self.masks = split_batch(latent_mask[None], frames_in_batch, num_ref_frames)[0]   # reduced ONCE
+        if strength_map is not None:   # (with mask_shape the hold above is ``support``'s, the map ``shaped``)
+            smap = self.mask_img if isinstance(strength_map, str) else _image_mask(strength_map, frames.shape[1], dev)
+            release, self.gate = ops.strength_release(smap, inf_pipe.num_ddim_steps, mask_mode, mask=self.mask_img)
+            self.release = release[None]
+            self.releases = split_batch(self.release, frames_in_batch, num_ref_frames)[0]   # built ONCE, split and joined as the mask is
 
     def window(self, k, R, init):
         """(initial latent, extra keywords) of window k, whose first R frames are carried over; ``init`` = the window's initial noise."""
@@ -313,15 +347,21 @@ class _EditPlan:
             kw["start_time"] = self.start_time
         if self.masks is not None:
             kw.update(mask=join(self.masks).contiguous(), source_latent=z, known_noise=init)
+        if self.releases is not None:
+            kw.update(release=join(self.releases).contiguous(), source_latent=z, known_noise=init)
         return latent, kw
+
+    def composite_mask(self):
+        """The image-resolution mask [T,H,W] of the final composite (and of ``stabilize``): the gate of a strength map, else the mask."""
+        return self.mask_img if self.gate is None else self.gate
 
     def finish(self, image, frames):
         """Decoded frames [1,T,3,H,W] -> the result: composited against the input outside the mask, clipped to [-1,1]."""
-        if self.mask_img is None:
+        if self.composite_mask() is None:
             return image.clip(-1, 1)
         img = image[0].to(torch.float32).contiguous()
         orig = frames[0].to(device=img.device, dtype=torch.float32).contiguous()
-        return ops.composite(img, orig, self.mask_img, out=img)[None]
+        return ops.composite(img, orig, self.composite_mask(), out=img)[None]
 
 
 def _stabilize(frames, image, params, flows, mask_img):
@@ -388,6 +428,7 @@ class _EditUnit:
         # the key-frame reduction: from here the unit's windows see the sub-video of its keys
         frames, cond, enc_noise = source, a["cond"], a["enc_noise"]
         self.full_mask = None
+        smap = a["strength_map"]
         if self.keys is not None:
             if mask is not None:   # the full-rate mask of the composite, shaped per frame exactly as the plan shapes the keys' rows
                 self.full_mask = _image_mask(mask, T, dev)
@@ -396,6 +437,11 @@ class _EditUnit:
                     self.full_mask, support = shape_mask(self.full_mask, **a["mask_shape"])
                     est = dict(est or {}, shaped=self.full_mask[None], support=support[None])
                 mask = mask if mask.shape[1] == 1 else mask[:, self.keys]
+            if smap is not None:   # the full-rate gate serves the fill's composite; the map itself is reduced to the keys as the mask is
+                full_map = self.full_mask if isinstance(smap, str) else _image_mask(smap, T, dev)
+                self.full_mask = ops.strength_release(full_map, pipe.num_ddim_steps, a["mask_mode"], mask=self.full_mask)[1]
+                if not isinstance(smap, str):
+                    smap = smap if smap.shape[1] == 1 else smap[:, self.keys]
             frames = source[:, self.keys]
             cond, enc_noise = (None if t is None else t[:, self.keys] for t in (cond, enc_noise))
         self.frames = frames
@@ -408,9 +454,12 @@ class _EditUnit:
             est = pipe.estimate_mask(cond * model.scale_factor if z is None else z, self.text["text_cond"], self.text["text_uncond"], cond,
                                      **kw, **_seeded(self.seed, self.unit))
             mask = est["mask"]
-        self.plan = _EditPlan(model, pipe, frames, cond, mask, a["strength"], a["mask_mode"], self.fib, self.nref, z=z, mask_shape=a["mask_shape"])
+        self.plan = _EditPlan(model, pipe, frames, cond, mask, a["strength"], a["mask_mode"], self.fib, self.nref, z=z, mask_shape=a["mask_shape"],
+                              **({} if smap is None else {"strength_map": smap}))
         if self.keys is None and self.plan.shape is not None:   # return_mask gains shaped / support (a drawn mask has no dict before that)
             est = dict(est or {}, **self.plan.shape)
+        if self.plan.release is not None:   # return_mask gains the release map (of the frames that are sampled) and the gate (of all frames)
+            est = dict(est or {}, release=self.plan.release, gate=(self.plan.gate if self.keys is None else self.full_mask)[None])
         self.est = est
         self.conds, self.refs = split_batch(cond, self.fib, self.nref)
         self.windows = len(self.conds)
@@ -457,7 +506,7 @@ class _EditUnit:
         image = self.plan.finish(self.model.decode_latent_to_image(latent), self.frames)
         if self.keys is None:
             if self.stab is not None:
-                image = _stabilize(self.source, image, self.stab, self.stab_flows, self.plan.mask_img)
+                image = _stabilize(self.source, image, self.stab, self.stab_flows, self.plan.composite_mask())
             return image, latent, self.est
         # the frames between the keys are filled along the source's flow; with a mask each of them is composited against the input with its
         # own mask exactly as the key frames were; the filter runs once, on the full-rate result.  The key frames stay bit for bit unless
@@ -487,7 +536,7 @@ def edit_video(model, inf_pipe, frames, text_cond, text_uncond, text_cfg=7.5, vi
                num_ref_frames=4, init_noises=None, enc_noise=None, flows_per_window=None, return_latent=False, cond=None,
                seed=None, unit=0, mask=None, strength=1.0, mask_mode="max", auto_mask=None, return_mask=False,
                mask_key=None, mask_flows=None, flow_estimator=None, mask_track=None, stabilize=None, stabilize_flows=None, mask_shape=None,
-               keyframes=None, key_flows=None):
+               strength_map=None, keyframes=None, key_flows=None):
     """frames [1,T,3,H,W] in [-1,1] -> edited frames [1,T,3,H,W] clipped to [-1,1].
 
     ``seed`` (default None: every draw comes from the global torch generators, as before) makes the edit reproducible: the posterior
@@ -549,7 +598,21 @@ def edit_video(model, inf_pipe, frames, text_cond, text_uncond, text_cfg=7.5, vi
     the input with its own mask (``mask_shape``: shaped at full rate), so outside it every delivered frame is the input's, bit for bit;
     ``stabilize`` runs once, on the full-rate result.  ``return_latent`` returns the key frames' latent; ``return_mask`` a dict that also
     holds ``keys`` and ``confidence`` [T,H,W] (1 on the key frames).  Not with ``mask="auto"``.  Untuned starting values, as the filter's.
-    Without ``keyframes`` nothing of this runs."""
+    Without ``keyframes`` nothing of this runs.
+
+    ``strength_map`` (a floating-point [1,T,H,W] or [1,1,H,W] tensor in [0,1], or the string "mask") gives every
+    pixel its own strength: the map is reduced per 8x8 latent cell like a mask (``mask_mode``), each cell's strength s is quantised like
+    ``strength`` (``schedulers.strength_to_start``) into the step that releases it, ``release = steps - n_exec(s)``, and inside the step
+    kernel the cell follows the source's re-noised latent through the steps before ``timesteps[release]`` and belongs to the model - under
+    its mask value, if there is a mask - from there on; a cell of strength 0 is never released.  The result is composited with the gate
+    ``G`` = 0 where the map is 0, elsewhere the unit's mask (or 1), so pixels of strength 0 ARE the input's; ``stabilize`` gets ``G`` as
+    the unit's mask.  ``"mask"``: the map is the unit's final image mask - drawn or tracked, after ``mask_shape`` - so a feathered edge
+    becomes a graded strength (with ``mask_shape`` the latent hold still comes from ``support``); it needs a mask, and not ``"auto"``
+    (hard).  ``strength`` keeps its meaning: it decides which steps run at all, so a map value above it changes nothing more - and no
+    step is skipped because no cell needs it (that would take a read-back): ``strength = max(map)`` saves those steps.  With
+    ``keyframes`` the map is reduced to the keys as the mask is and the full-rate ``G`` serves the fill.  ``return_mask=True`` then
+    returns a dict that also holds ``release`` [1,T,h,w] (int32; of the key frames with ``keyframes``) and ``gate`` [1,T,H,W].  Without
+    ``strength_map`` nothing of this runs."""
     args = {k: v for k, v in locals().items() if k in UNIT_KEYS}
     _check_unit(frames.shape, args)
     u = _EditUnit(model, inf_pipe, frames, text_cond, text_uncond, frames_in_batch, num_ref_frames, seed, unit, flow_estimator, args).prepare()
@@ -586,7 +649,8 @@ def edit_videos(model, inf_pipe, units, frames_in_batch=16, num_ref_frames=4, re
     mask is shaped alone, before the stacked windows start, bit for bit as ``edit_video`` shapes it.  A unit may carry ``keyframes`` (and
     ``key_flows``) as for ``edit_video``: the units' SUB-VIDEOS of key frames are what stack - they must share a shape, under the same
     ValueError - and each unit is filled alone, after the stacked windows, bit for bit as ``edit_video`` fills it; its latent is its key
-    frames'."""
+    frames'.  A unit may carry ``strength_map`` as for ``edit_video``: its release map is built alone, before the stacked windows start;
+    mapped, masked and plain units stack together (``strength`` still has to be shared)."""
     if len(units) == 0:
         return []
     for u in units:
@@ -673,6 +737,14 @@ def build_parser():
                    help="feather the mask over F pixels OUTSIDE its (grown) edge, [0, 32]: the composite blends there, the latent is free there")
     p.add_argument("--mask-profile", type=str, default=None, help="linear | smooth (default): the feather's ramp")
     p.add_argument("--mask-threshold", type=float, default=None, help="a pixel is inside the mask where its value exceeds this (default 0.5)")
+    p.add_argument("--strength-map", type=str, default=None,
+                   help="per-pixel edit strength (DESIGN.md section 28): a .pt tensor [1,T,H,W] or [1,1,H,W] in [0,1], or an image / a directory "
+                        "of images read like --mask-image (white = fully re-drawn, black = never touched); every unit gets it; a --units file "
+                        "may carry its own \"strength_map\" entry [n,T,H,W] or [n,1,H,W] instead.  No step is skipped because no pixel "
+                        "needs it: --strength max(map) saves those steps")
+    p.add_argument("--strength-from-mask", action="store_true",
+                   help="every unit's final mask (drawn or tracked, after --mask-grow / --mask-feather) is its strength map: a feathered edge "
+                        "becomes a graded strength; needs a drawn mask (--mask-file, --mask-image, --synthetic-mask, the \"mask\" entry of a --units file)")
     p.add_argument("--mask-key", type=int, default=None,
                    help="the frame the masks are drawn on ([1,1,H,W] each): they follow the motion through the video (insv2v/mask_track.py); the "
                         "flows come from the estimator of --raft-ckpt (--synthetic: key-hashed weights)")
@@ -778,6 +850,17 @@ def check_args(args):
         if not (mask_file or mask_image or getattr(args, "auto_mask", False) or getattr(args, "synthetic_mask", False) or args.units):
             raise SystemExit("--mask-grow / --mask-feather / --mask-profile / --mask-threshold shape a mask: they need --mask-file, --mask-image, "
                              "--auto-mask, --synthetic-mask or the \"mask\" entry of a --units file")
+    smap, from_mask = getattr(args, "strength_map", None), getattr(args, "strength_from_mask", False)
+    if smap and from_mask:
+        raise SystemExit("--strength-map and --strength-from-mask are two strength maps: pass one")
+    if smap and not os.path.exists(smap):
+        raise SystemExit(f"--strength-map {smap} is neither a file nor a directory")
+    if smap and getattr(args, "region", False):
+        raise SystemExit("--strength-map with --region: a map is not resampled to the working clip (not built); --strength-from-mask works there")
+    if from_mask and getattr(args, "auto_mask", False):
+        raise SystemExit("--strength-from-mask and --auto-mask: an estimated mask is hard (0 or 1), it grades nothing; pass --strength-map")
+    if from_mask and not (mask_file or mask_image or getattr(args, "synthetic_mask", False) or args.units):
+        raise SystemExit("--strength-from-mask needs a mask: --mask-file FILE.pt, --mask-image PATH, the \"mask\" entry of a --units file, or --synthetic-mask")
     if mask_key is not None:
         if getattr(args, "auto_mask", False):
             raise SystemExit("--mask-key tracks a drawn mask and --auto-mask estimates one per frame: pass one")
@@ -982,6 +1065,29 @@ def mask_shape_unit(args):
     return dict(mask_shape=given) if given else {}
 
 
+def load_strength_map(args, width, height):
+    """The map of --strength-map at the frames' size ([1,1,H,W] or [1,T,H,W]; None without it): a .pt tensor as it is, images through
+    ``video_io.load_mask``."""
+    path = getattr(args, "strength_map", None)
+    if not path:
+        return None
+    if path.lower().endswith(".pt"):
+        m = torch.load(path, map_location="cpu")
+        if not torch.is_tensor(m) or m.dim() != 4 or m.shape[0] != 1:
+            raise SystemExit("--strength-map FILE.pt must hold a tensor [1,T,H,W] or [1,1,H,W]")
+        return m
+    from .video_io import load_mask
+    return load_mask(path, (width, height))
+
+
+def strength_map_unit(args, has_mask, smap=None):
+    """What --strength-from-mask (a unit with a mask) or a strength map (``smap``: --strength-map's, or the unit's entry of a --units
+    file) adds to a unit - nothing without them."""
+    if getattr(args, "strength_from_mask", False):
+        return dict(strength_map="mask") if has_mask else {}
+    return {} if smap is None else dict(strength_map=smap)
+
+
 def region_unit(args, image_size=None):
     """What --region adds to every unit (nothing without it): ``region=`` of ``region.edit_region`` with the working size --image-size
     (``image_size``: that of one combination) and only the values given; the others keep ``check_region``'s defaults.  Without
@@ -1009,7 +1115,7 @@ def region_est(args, est):
     taken at the source's, so only the drawn mask splits them."""
     if not getattr(args, "region", False) or est is None:
         return est
-    return {k: v for k, v in est.items() if k not in ("shaped", "support", "mask")}
+    return {k: v for k, v in est.items() if k not in ("shaped", "support", "mask", "release", "gate")}
 
 
 def load_mask_image(args, width, height):
@@ -1054,7 +1160,7 @@ def write_masks(path, records, rank=0, world=1):
     """{unit id: {"mask_latent": [T,h,w], "soft": [T,h,w]}} (estimated, --auto-mask) or {unit id: {"mask": [T,H,W], "valid": [T,H,W]}}
     (tracked, --mask-key) of this rank's units (with several ranks each writes its own FILE.rankR.pt).  A shaped run (--mask-grow /
     --mask-feather) writes every unit's "shaped" and "support" [T,H,W] next to whatever its source returned."""
-    records = {u: est for u, est in records.items() if est is not None and set(est) - {"keys", "confidence"}}   # (a unit the mask file does not name has none)
+    records = {u: est for u, est in records.items() if est is not None and set(est) - {"keys", "confidence", "release", "gate"}}   # (a unit the mask file does not name has none)
     if any("shaped" in est for est in records.values()):   # --mask-grow / --mask-feather: what the source gave, and the two shaped masks
         keys = ("mask", "valid", "mask_latent", "soft", "shaped", "support")
     elif any("valid" in est for est in records.values()):
@@ -1130,6 +1236,7 @@ def run_dataset(args, model, pipe, rank=0, world=1, scorer=None):
             drawn = {batch["video_name"]: load_mask_image(args, *((None, None) if on_region else (image_size, image_size)))}
         # once per video, shared by the four prompts (:98); a region edit encodes its own working clip
         cond = None if on_region else model.encode_image_to_latent(frames, **_seeded(seed, 4 * ci)) / model.scale_factor
+        smap = load_strength_map(args, image_size, image_size)
         todo = []
         for key in kinds:
             prompt = prompts[batch["video_name"]]["edit_" + key] if args.prompt_source == "edit" else batch[key]
@@ -1142,6 +1249,7 @@ def run_dataset(args, model, pipe, rank=0, world=1, scorer=None):
                                                    text_cfg=text_cfg, video_cfg=video_cfg, unit=4 * ci + kinds.index(key),
                                                    **({"cond": cond} if cond is not None else {}), **region_unit(args, image_size),
                                                    strength=getattr(args, "strength", 1.0), **per["all"], **per["masked"](batch["video_name"] in drawn),
+                                                   **strength_map_unit(args, batch["video_name"] in drawn, smap),
                                                    **(dict(mask=drawn[batch["video_name"]], mask_mode=getattr(args, "mask_mode", "max"))
                                                       if batch["video_name"] in drawn else {})), prompt))
         # the four prompts of a video share the conditioning latent and the window plan: one stacked launch chain per window (B = 12)
@@ -1239,10 +1347,14 @@ def main(argv=None):
     per, more, want_masks, estimator = cli_options(args, f"cuda:{local}", data)   # (refuses --auto-mask next to a "mask" entry of the file)
     est_masks = {}
     masks = data.get("mask")   # optional [n,T,H,W] / [n,1,H,W]
+    smaps, smap_cli = data.get("strength_map"), load_strength_map(args, data["frames"].shape[-1], data["frames"].shape[-2])   # optional [n,T,H,W] / [n,1,H,W]
+    if smaps is not None and (smap_cli is not None or args.strength_from_mask):
+        raise SystemExit("--strength-map / --strength-from-mask next to the \"strength_map\" entry of the --units file are two strength maps: pass one")
 
     def edit(i):
         m = masks[i:i + 1] if masks is not None else drawn.get(i, image_mask)
-        return dict(dict(mask=m, strength=args.strength, mask_mode=args.mask_mode), **per["all"], **per["masked"](m is not None))
+        return dict(dict(mask=m, strength=args.strength, mask_mode=args.mask_mode), **per["all"], **per["masked"](m is not None),
+                    **strength_map_unit(args, m is not None, smaps[i:i + 1] if smaps is not None else smap_cli))
     region = region_unit(args)   # with it the drivers are region.edit_region / edit_regions around the same calls
     scorer = build_scorer(args, f"cuda:{local}", tok)
     records = []
